@@ -7,25 +7,30 @@ One STEP = one cost volume as GA-Net feeds the ops at crop 240x624, max_disp 192
   + Lga2Function fwd+bwd (radius 2, two chained passes) on x [1,193,240,624], f [1,75,240,624]
 fp32, synthetic inputs resident in HBM before the timed region, torch.manual_seed(123).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 N > 1 is launched by the driver as torch.distributed.run, one rank per GPU (without a launcher this file re-executes
 itself that way); ranks run independent cost volumes (the ops have no cross-sample term, so there is no data-path
 collective; the barrier / max-over-ranks timing protocol runs over gloo on the host): weak scaling,
-value = N*K / max-over-ranks time.  After the timed region the ranks run the one collective a data-parallel caller of this
-path has -- the 26.3 MB fp32 gradient all-reduce of GANet-deep -- over RCCL and report it as `rccl` (never part of
-`value`).  Rank 0 prints ONE JSON line.
+value = N*K / max-over-ranks time.  Rank 0 prints ONE JSON line.
 
-Extra objects in the line:
+A plain run sets up, captures the step into a hipGraph, replays it W times, times K replays and prints the line
+(`value`, `ms_per_step` = the time of one timed step).  --dump-outputs DIR writes what the last timed step computed
+-- the SGA output and its five gradients, the LGA2 output and its two gradients -- as DIR/<name>.npy in float32, each a
+fixed seeded sample of DUMP_ELEMS elements (the inputs are seeded: two builds compare output for output).
+
+--full adds the extra measurements, each after the timed region and never part of `value`:
   roofline      ONE kernel under the name rocprofv3 prints for it -- the launch with the largest share of the step -- against its
                 binding bound (HBM bandwidth for the SGA kernels, fp32 FMA rate for the LGA kernels), from HIP-event
                 timings of every kernel in place on the launch stream after the timed region; `kernels` lists all 16 launches,
                 `families` the six kernel families with both fractions, `dominant_family` / `worst_family` name the family with
                 the largest share and the one furthest below its bound; the measured traffic (PMC) beside the algorithmic bytes
-  value         the contract's protocol: W warm-up replays + K timed ones straight after the graph capture; `value_settled` = the
-                same K steps after 0.1 s more of replays (the clock ramp after the capture is worth ~1.5 %), `value_1s` sustained
+  value_settled the same K steps after 0.1 s more of replays (the clock ramp after the capture is worth ~1.5 %), `value_1s` sustained
   cpu_baseline  the CPU checker (oracle/_ref = the reference's own kernel bodies when the prebuilt
                 .so is present, else the C restatement) timed on this box's host cores on ONE
                 cost volume of the same workload
+  eager_ms_per_step, two_stream_ms_per_step   the step launched eagerly from Python; its SGA and LGA halves on two streams
+  rccl          (N > 1) the one collective a data-parallel caller of this path has -- the 26.3 MB fp32 gradient all-reduce of
+                GANet-deep -- over RCCL
 """
 import argparse
 import json
@@ -77,13 +82,33 @@ def make_inputs(device):
 
 
 def one_step(inp):
+    """-> (SGA output, its gradients w.r.t. x and the four guidance tensors, LGA2 output, its gradients w.r.t. x and f)"""
     from ganet_amd.functions.GANet import Lga2Function, SgaFunction
     x, gs, go, xl, f, gy = inp
     out = SgaFunction.apply(x, *gs)
     g1 = torch.autograd.grad(out, [x] + gs, go)
     y = Lga2Function.apply(xl, f, RADIUS)
     g2 = torch.autograd.grad(y, [xl, f], gy)
-    return g1, g2
+    return out, g1, y, g2
+
+
+OUTPUT_NAMES = ["sga_out", "sga_grad_x", "sga_grad_g0", "sga_grad_g1", "sga_grad_g2", "sga_grad_g3",
+                "lga2_out", "lga2_grad_x", "lga2_grad_f"]
+DUMP_ELEMS = 1 << 20          # per array: nine float32 samples of 4 MiB, 36 MiB in all
+
+
+def dump_outputs(step_result, d):
+    """one_step's arrays -> d/<name>.npy, float32: the same DUMP_ELEMS flat indices of every array (seeded, sorted) where it is
+    larger, the whole array otherwise."""
+    import numpy as np
+    out, g1, y, g2 = step_result
+    os.makedirs(d, exist_ok=True)
+    for name, t in zip(OUTPUT_NAMES, [out, *g1, y, *g2]):
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(flat.numel(), DUMP_ELEMS, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(d, name + ".npy"), flat.float().cpu().numpy())
 
 
 def one_step_two_streams(inp, side):
@@ -477,13 +502,14 @@ def stub_main(args):
     if ctx.rank == 0:
         print("[bench] measured: " + json.dumps(line), file=sys.stderr, flush=True)
     # the protocol test's stand-in for the RCCL probe of the real run: same code path (child processes, own rendezvous), gloo
-    delay = float(os.environ.get("GANET_BENCH_TEST_DELAY_RANK0", "0"))
-    if delay and ctx.rank == 0:
-        time.sleep(delay)
-    probe = gdist.allreduce_probe_isolated(ctx, "gloo", 0, timeout_s=float(os.environ.get("GANET_BENCH_PROBE_TIMEOUT", "150")),
-                                           nelem=1 << 16, iters=2)
-    if probe is not None:
-        line["rccl"] = probe
+    if args.full:
+        delay = float(os.environ.get("GANET_BENCH_TEST_DELAY_RANK0", "0"))
+        if delay and ctx.rank == 0:
+            time.sleep(delay)
+        probe = gdist.allreduce_probe_isolated(ctx, "gloo", 0, timeout_s=float(os.environ.get("GANET_BENCH_PROBE_TIMEOUT", "150")),
+                                               nelem=1 << 16, iters=2)
+        if probe is not None:
+            line["rccl"] = probe
     gdist.finish(ctx)
     if ctx.rank == 0:
         print(json.dumps(line))
@@ -518,8 +544,15 @@ def main():
     ap.add_argument("--no-overlap", dest="overlap", action="store_false",
                     help="skip the extra measurement of the step with its SGA and LGA halves on two streams "
                          "(`two_stream_ms_per_step`: an extra field, never `value`)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure value_settled, value_1s, the eager and two-stream step times, the "
+                         "per-kernel roofline, the CPU baseline and (N > 1) the RCCL all-reduce")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, seeded samples)")
     ap.add_argument("--stub-step", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))
@@ -579,57 +612,68 @@ def main():
         # (scripts/diag_bench_timing.py, profiles/r7k_diag_bench_timing.txt); W = 5 warm-up steps are 8 ms.  Rounds 4 - 5 therefore
         # replayed for SETTLE_S seconds first and printed THAT measurement as `value`; since round 6:
         # `value` IS the contract's protocol: W warm-up replays and K timed ones straight after the capture (`--warmup 5`
-        # means what the driver typed).  The same K steps once the device is back at its running clocks (SETTLE_S seconds of
-        # replays, then W + K again) are reported beside it as `value_settled`; `value_1s` is the sustained rate.
-        for _ in range(args.warmup):
-            graph.replay()
-        elapsed = gdist.timed_region(ctx, lambda: [graph.replay() for _ in range(args.steps)],
-                                     sync=torch.cuda.synchronize)
-        t_settle = time.perf_counter()
-        while time.perf_counter() - t_settle < SETTLE_S:
-            for _ in range(10):
+        # means what the driver typed).  With --full the same K steps once the device is back at its running clocks (SETTLE_S
+        # seconds of replays, then W + K again) are reported beside it as `value_settled`; `value_1s` is the sustained rate.
+        def run_block():
+            for _ in range(args.steps):
                 graph.replay()
-            torch.cuda.synchronize()
+
         for _ in range(args.warmup):
             graph.replay()
-        elapsed_settled = gdist.timed_region(ctx, lambda: [graph.replay() for _ in range(args.steps)],
-                                             sync=torch.cuda.synchronize)
-        value_settled = ctx.world_size * args.steps / elapsed_settled
+        elapsed = gdist.timed_region(ctx, run_block, sync=torch.cuda.synchronize)
+        last = keep                           # the graph's outputs hold what its last replay computed
     else:
+        def run_block():
+            nonlocal last
+            for _ in range(args.steps):
+                last = one_step(inp)
+
         for _ in range(args.warmup):
             one_step(inp)
-        elapsed = gdist.timed_region(ctx, lambda: [one_step(inp) for _ in range(args.steps)],
-                                     sync=torch.cuda.synchronize)
-        value_settled = None
+        last = None
+        elapsed = gdist.timed_region(ctx, run_block, sync=torch.cuda.synchronize)
     value = ctx.world_size * args.steps / elapsed
-    if graph is not None:
-        value_1s, n_blocks = sustained_rate(ctx, lambda: [graph.replay() for _ in range(args.steps)], args.steps)
-    else:
-        value_1s, n_blocks = sustained_rate(ctx, lambda: [one_step(inp) for _ in range(args.steps)], args.steps)
+    if args.dump_outputs and ctx.rank == 0:
+        dump_outputs(last, args.dump_outputs)
+    protocol = "value = W warm-up + K timed replays straight after the graph capture (the contract)"
+    if args.full:
+        protocol += "; value_settled = the same after settle_s more of replays; value_1s = median block over >= 1 s"
+        value_settled = None
+        if graph is not None:
+            t_settle = time.perf_counter()
+            while time.perf_counter() - t_settle < SETTLE_S:
+                for _ in range(10):
+                    graph.replay()
+                torch.cuda.synchronize()
+            for _ in range(args.warmup):
+                graph.replay()
+            elapsed_settled = gdist.timed_region(ctx, run_block, sync=torch.cuda.synchronize)
+            value_settled = ctx.world_size * args.steps / elapsed_settled
+        value_1s, n_blocks = sustained_rate(ctx, run_block, args.steps)
 
     line = {
         "metric": "cost-volumes/sec (SGA+LGA fwd+bwd) at 240x624x192",
         "value": round(value, 2), "unit": "cost-volumes/sec", "n_gpus": ctx.world_size,
         "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(1e3 * elapsed / args.steps, 4),
-        "value_1s": round(value_1s, 2), "value_1s_blocks": n_blocks,
-        "value_settled": round(value_settled, 2) if value_settled is not None else None,
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "f32", "data": "synthetic",
         "config": {"workload": "configs[1]: SGA fwd+bwd [1,32,65,80,208] (4x guidance [1,32,5,80,208]) + "
                                "LGA2 r=2 fwd+bwd [1,193,240,624] (filters [1,75,240,624]), one sample per GPU",
                    "parallelism": "independent cost volumes per GPU, no data-path collective",
                    "launch": launch_mode,
-                   "protocol": "value = W warm-up + K timed replays straight after the graph capture (the contract); value_settled = the same "
-                               "after settle_s more of replays; value_1s = median block over >= 1 s",
-                   "settle_s": SETTLE_S if graph is not None else 0.0},
+                   "protocol": protocol},
         "unit_alg_bytes": UNIT_BYTES,
         "unit_hbm_frac": round(value / ctx.world_size * UNIT_BYTES / (HBM_PEAK_GBS * 1e9), 4),
     }
+    if args.full:
+        line.update({"value_1s": round(value_1s, 2), "value_1s_blocks": n_blocks,
+                     "value_settled": round(value_settled, 2) if value_settled is not None else None})
+        line["config"]["settle_s"] = SETTLE_S if graph is not None else 0.0
     if ctx.rank == 0:
         # the measured value is on record before anything else runs (stderr; the ONE stdout line comes last)
         print("[bench] measured: " + json.dumps(line), file=sys.stderr, flush=True)
-    if ctx.world_size > 1:
+    if args.full and ctx.world_size > 1:
         # The gradient all-reduce of a data-parallel caller (26.3 MB fp32 = GANet-deep's parameters) over RCCL / xGMI: AFTER the
         # timed region, BEFORE rank 0's extra measurements (ranks 1..N-1 never sit in a collective with a timeout while rank 0
         # is busy), on every rank, in child processes of their own (gdist.allreduce_probe_isolated: a hung or failed RCCL call
@@ -638,7 +682,7 @@ def main():
         if delay and ctx.rank == 0:
             time.sleep(delay)
         line["rccl"] = gdist.allreduce_probe_isolated(ctx, os.environ.get("GANET_BENCH_COLLECTIVE", "nccl"), device.index)
-    if ctx.rank == 0:
+    if args.full and ctx.rank == 0:
         if graph is not None:
             # for reference: the same step launched eagerly from Python (host-speed dependent)
             torch.cuda.synchronize()

@@ -8,8 +8,8 @@
  * Parity status: PINNED against the reference's own kernel arithmetic.  The
  * reference ships no tests or golden vectors, so the pin is
  * (a) oracle/_ref (the reference's __global__ bodies host-compiled through
- * oracle/ref_shim, see oracle/Makefile) compared with this file in
- * tests/test_oracle_vs_ref.py whenever /root/reference is present, and
+ * oracle/ref_shim, see oracle/Makefile) compared with this file on the
+ * awkward shapes of tests/test_oracle_vs_ref.py, and
  * (b) tests/golden/*.npz generated from oracle/_ref by
  * tests/golden/make_golden.py and committed.
  *

@@ -40,11 +40,11 @@ if has smoke; then
 fi
 if has bench; then
   echo "== bench"
-  timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cat $OUT/bench.json; tail -5 $OUT/bench.err
+  timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cat $OUT/bench.json; tail -5 $OUT/bench.err
 fi
 if has prof; then
   echo "== rocprof kernel trace (bench)"
-  ( cd /tmp; timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/prof -o trace --output-format csv -- python $ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline > $OUT/rocprof.log 2>&1; echo "rocprof rc=$?" )
+  ( cd "$TMPDIR"; timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/prof -o trace --output-format csv -- python $ROOT/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $OUT/rocprof.log 2>&1; echo "rocprof rc=$?" )
   find $OUT/prof -name '*kernel_stats*' | head -1 | xargs -r head -16
 fi
 if has pmc; then

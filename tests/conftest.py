@@ -17,10 +17,3 @@ def port_oracle():
     from oracle.oracle import Oracle
     return Oracle("port")
 
-
-@pytest.fixture(scope="session")
-def ref_oracle():
-    from oracle import oracle
-    if not oracle.have("reference") and not os.path.exists("/root/reference"):
-        pytest.skip("oracle/_ref not built and /root/reference absent")
-    return oracle.Oracle("reference")

@@ -4,6 +4,8 @@ Run in the dev container only (needs /root/reference to build oracle/_ref):
     python tests/golden/make_golden.py              the small fixtures (tests/golden/*.npz)
     python tests/golden/make_golden.py --digests    sha256 of every output of the reference at the FULL model shapes
                                                     (BASELINE configs[1] and the SGA-B / cfg3 volumes) -> tests/golden/digests.json
+    python tests/golden/make_golden.py --vs-ref     inputs and outputs of the reference on the awkward shapes of
+                                                    tests/test_oracle_vs_ref.py -> tests/golden/vs_ref_golden.npz
 Every output array below comes from oracle/_ref/libganet_ref.so, i.e. from
 /root/reference/libs/GANet/src/GANet_kernel.cu compiled through oracle/ref_shim
 with the launch order of its host launchers (GANet_kernel.cu:935-1129, 1271-1364)
@@ -123,5 +125,27 @@ def digests():
         fh.write("\n")
 
 
+def vs_ref():
+    ref = Oracle("reference")
+    out = {}
+    for shape in gu.VS_REF_SGA_SHAPES:
+        k = gu.vs_ref_key("sga", shape)
+        x, gs, go = gu.vs_ref_sga_inputs(shape)
+        o, tmp, mask = ref.sga_forward(x, *gs)
+        grads = ref.sga_backward(x, *gs, tmp, mask, go)
+        out.update({f"{k}.x": x, f"{k}.go": go, f"{k}.out": o, f"{k}.temp_out": tmp, f"{k}.mask": mask})
+        for d in range(4):
+            out[f"{k}.g{d}"] = gs[d]
+        out.update({f"{k}.{n}": g for n, g in zip(("gx", "gw0", "gw1", "gw2", "gw3"), grads)})
+    for shape, r in gu.VS_REF_LGA_CASES:
+        k = gu.vs_ref_key("lga", shape, r)
+        x, f, gy = gu.vs_ref_lga_inputs(shape, r)
+        gx, gf = ref.lga_backward(x, f, gy, r)
+        out.update({f"{k}.x": x, f"{k}.f": f, f"{k}.gy": gy, f"{k}.y": ref.lga_forward(x, f, r), f"{k}.gx": gx, f"{k}.gf": gf})
+    fn = os.path.join(HERE, "vs_ref_golden.npz")
+    np.savez_compressed(fn, **out)
+    print(fn, os.path.getsize(fn), "bytes")
+
+
 if __name__ == "__main__":
-    digests() if "--digests" in sys.argv else main()
+    digests() if "--digests" in sys.argv else vs_ref() if "--vs-ref" in sys.argv else main()

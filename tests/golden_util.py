@@ -101,3 +101,32 @@ def lga_digests(ora, shape, seed):
     return d
 
 
+
+
+# ---- the restatement against the reference on awkward shapes (tests/test_oracle_vs_ref.py <- tests/golden/vs_ref_golden.npz,
+# made by make_golden.py --vs-ref from oracle/_ref: inputs and every output of the reference, so the test needs no oracle/_ref) ---
+VS_REF_SGA_SHAPES = [(1, 2, 5, 4, 3), (2, 2, 16, 7, 5), (1, 3, 34, 9, 17), (1, 1, 3, 2, 33)]
+VS_REF_LGA_CASES = [((1, 6, 5, 7), 1), ((2, 9, 6, 11), 2), ((1, 2, 4, 3, 9), 2), ((1, 4, 3, 3), 3)]   # (shape, radius)
+
+
+def vs_ref_key(op, shape, r=None):
+    return op + "_" + "x".join(map(str, shape)) + ("" if r is None else f"_r{r}")
+
+
+def vs_ref_sga_inputs(shape):
+    rng = np.random.default_rng(sum(shape))
+    N, C, D, H, W = shape
+    x = rng.standard_normal(shape).astype(np.float32)
+    gs = [_l1norm(rng.standard_normal((N, C, 5, H, W)), 2) for _ in range(4)]
+    go = rng.standard_normal(shape).astype(np.float32)
+    return x, gs, go
+
+
+def vs_ref_lga_inputs(shape, r):
+    rng = np.random.default_rng(sum(shape) + r)
+    fs = list(shape)
+    fs[-3] = 3 * (2 * r + 1) ** 2
+    x = rng.standard_normal(shape).astype(np.float32)
+    f = _l1norm(rng.standard_normal(fs), -3)
+    gy = rng.standard_normal(shape).astype(np.float32)
+    return x, f, gy

@@ -111,10 +111,15 @@ def test_pure_torch_losses_match_reference_formulas():
     assert torch.allclose(y[0], torch.tensor([0.25, -0.75]), atol=1e-5)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/models/GANet_deep.py"), reason="reference tree absent")
+def _model_root():
+    from harness import refmodel
+    return refmodel.model_root()
+
+
+@pytest.mark.skipif(_model_root() is None, reason="no reference model code found (harness.refmodel.model_root)")
 def test_reference_models_import_on_top_of_the_drop_in(monkeypatch):
     """models/GANet_deep.py and GANet11.py construct unchanged with this repo's `libs` package."""
-    monkeypatch.syspath_prepend("/root/reference")
+    monkeypatch.syspath_prepend(_model_root())
     monkeypatch.syspath_prepend(ROOT)
     for m in [k for k in sys.modules if k == "models" or k.startswith("models.")]:
         monkeypatch.delitem(sys.modules, m)

@@ -76,7 +76,7 @@ def test_bench_gpus2_plumbing_with_stub_step(launcher):
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     bench = os.path.join(ROOT, "bench.py")
-    tail = [bench, "--gpus", "2", "--steps", "3", "--warmup", "1", "--stub-step"]
+    tail = [bench, "--gpus", "2", "--steps", "3", "--warmup", "1", "--stub-step", "--full"]
     if launcher == "self":
         cmd = [sys.executable] + tail
     else:
@@ -102,7 +102,7 @@ def _run_stub_bench(extra_env, timeout=300):
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(extra_env)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--stub-step"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--stub-step", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

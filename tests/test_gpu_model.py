@@ -144,11 +144,7 @@ import os, shutil, sys, glob, tempfile
 import numpy as np
 import torch
 root = sys.argv[1]
-src = os.path.join(root, "oracle", "_ref", "pyref", "modeB")
-if os.path.exists("/root/reference/libs/GANet/functions/GANet.py"):
-    src_libs = "/root/reference/libs"           # the real files where they exist
-else:
-    src_libs = os.path.join(src, "libs")
+src_libs = os.path.join(root, "oracle", "_ref", "pyref", "modeB", "libs")
 tmp = tempfile.mkdtemp()
 dst = os.path.join(tmp, "libs", "GANet")
 for sub in ("functions", "modules"):
@@ -208,12 +204,11 @@ shutil.rmtree(tmp)
 
 
 def test_reference_python_layer_unmodified_on_the_pybind_module(env):
-    """INTEGRATION.md mode B: the reference's OWN libs/GANet/functions/GANet.py and modules/GANet.py (its files where
-    /root/reference exists, their byte-compiled form from oracle/_ref/pyref on the GPU box -- never vendored) import this
+    """INTEGRATION.md mode B: the reference's OWN libs/GANet/functions/GANet.py and modules/GANet.py (their byte-compiled
+    form from oracle/_ref/pyref -- never vendored) import this
     repository's pybind module through their unchanged `from ..build.lib import GANet` and match the oracle: SGA forward
     bit-exact, SGA / LGA2 gradients within 1e-4.  Runs in a fresh interpreter so that `libs` is the reference's package."""
-    have_src = os.path.exists("/root/reference/libs/GANet/functions/GANet.py") or \
-        os.path.exists(os.path.join(ROOT, "oracle", "_ref", "pyref", "modeB", "libs", "GANet", "functions", "GANet.pyc"))
+    have_src = os.path.exists(os.path.join(ROOT, "oracle", "_ref", "pyref", "modeB", "libs", "GANet", "functions", "GANet.pyc"))
     if not have_src:
         pytest.skip("the reference's functions/GANet.py is not available in any form")
     env_ = {k: v for k, v in os.environ.items() if k != "PYTHONPATH"}
