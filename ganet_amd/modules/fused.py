@@ -12,14 +12,26 @@ __all__ = ["GuidedSGA", "GuidedSGABnRelu", "NormalizedLGA2", "NormDisparityRegre
            "DispAggTail", "TrilinearUpsample", "ResidualBnRelu", "folded_bn"]
 
 
-def folded_bn(bn):
+def folded_bn(bn, refresh=False):
     """(scale, shift) with bn(x) == scale[c] * x + shift[c] for a BatchNorm in eval mode (running statistics).  The pair is
-    kept on the module and recomputed when any of its four tensors has been written since (their autograd version counters):
-    six tiny launches per call otherwise, which is what an SGABlock tail on a 26 MB volume costs altogether."""
+    kept on the module and recomputed when any of its tensors has been written since: six tiny launches per call otherwise,
+    which is what an SGABlock tail on a 26 MB volume costs altogether.
+
+    What "written since" sees: the autograd version counters of running_mean / running_var / weight / bias (optimizer steps,
+    copy_, load_state_dict) AND of num_batches_tracked -- a train-mode forward updates the running statistics inside
+    batch_norm without bumping THEIR counters, but the module counts the batch with an in-place add first.  A module met in
+    training mode gets its pair dropped and none kept.  All of this is host-side bookkeeping: no launch, no synchronisation
+    on the steady eval path.  A write that bypasses the counters altogether (through `.data`, through a raw pointer, or a
+    functional batch_norm called on the buffers) is invisible to any host-side key; seeing it would take a comparison of
+    values on the device and a synchronisation per call.  After such a write call folded_bn(bn, refresh=True) once."""
+    if bn.training:
+        bn.__dict__.pop("_ganet_folded", None)
+        refresh = True
     src = (bn.running_mean, bn.running_var) + ((bn.weight, bn.bias) if bn.affine else ())
-    key = tuple((t.data_ptr(), t._version) for t in src) + (bn.eps,)
+    nbt = getattr(bn, "num_batches_tracked", None)
+    key = tuple((t.data_ptr(), t._version) for t in src + ((nbt,) if nbt is not None else ())) + (bn.eps,)
     hit = bn.__dict__.get("_ganet_folded")
-    if hit is not None and hit[0] == key:
+    if not refresh and hit is not None and hit[0] == key:
         return hit[1]
     with torch.no_grad():
         scale = torch.rsqrt(bn.running_var + bn.eps)
@@ -29,7 +41,8 @@ def folded_bn(bn):
         else:
             shift = -bn.running_mean * scale
         pair = (scale.float().contiguous(), shift.float().contiguous())
-    bn.__dict__["_ganet_folded"] = (key, pair)       # not a buffer, not a parameter: state_dict keys stay the reference's
+    if not bn.training:
+        bn.__dict__["_ganet_folded"] = (key, pair)   # not a buffer, not a parameter: state_dict keys stay the reference's
     return pair
 
 

@@ -6,6 +6,12 @@ Run in the dev container only (needs /root/reference to build oracle/_ref):
                                                     (BASELINE configs[1] and the SGA-B / cfg3 volumes) -> tests/golden/digests.json
     python tests/golden/make_golden.py --vs-ref     inputs and outputs of the reference on the awkward shapes of
                                                     tests/test_oracle_vs_ref.py -> tests/golden/vs_ref_golden.npz
+    python tests/golden/make_golden.py --values     the tie-heavy / exactly representable input families of
+                                                    tests/parity_cases.py on shapes that reach the fast kernels
+                                                    -> tests/golden/sga_values_golden.npz, sga_values_sparse_golden.npz,
+                                                    lga_values_golden.npz
+    python tests/golden/make_golden.py --value-digests   ADDS sga_cfg2_select and lga2_cfg2_exact to digests.json
+                                                    (the entries already there are kept as they are, not recomputed)
 Every output array below comes from oracle/_ref/libganet_ref.so, i.e. from
 /root/reference/libs/GANet/src/GANet_kernel.cu compiled through oracle/ref_shim
 with the launch order of its host launchers (GANet_kernel.cu:935-1129, 1271-1364)
@@ -147,5 +153,56 @@ def vs_ref():
     print(fn, os.path.getsize(fn), "bytes")
 
 
+def values():
+    import parity_cases as pc
+    ref = Oracle("reference")
+    out = {}
+    for fam in gu.VALUES_SGA_FAMILIES:
+        for tag, shape in gu.VALUES_SGA_SHAPES:
+            name = f"{fam}_{tag}"
+            x, gs, go = pc.SGA_FAMILIES[fam](shape, sum(shape))
+            o, tmp, mask = ref.sga_forward(x, *gs)
+            grads = ref.sga_backward(x, *gs, tmp, mask, go)
+            out.update({f"{name}.x": x, f"{name}.go": go, f"{name}.out": o, f"{name}.tmp": tmp,
+                        f"{name}.mask": mask.astype(np.uint8), f"{name}.gx": grads[0]})
+            for d in range(4):
+                out[f"{name}.g{d}"] = gs[d]
+                out[f"{name}.A{d}"] = ref.sga_scan(x, gs[d], d)
+                out[f"{name}.gw{d}"] = grads[1 + d]
+    # two files, so that each stays well under the 1 MiB limit for a committed file (the *sparse* cases hardly compress)
+    for fn, fams in gu.VALUES_SGA_FILES:
+        np.savez_compressed(os.path.join(HERE, fn), **{k: v for k, v in out.items() if k.split("_")[0] in fams})
+    out = {}
+    for name, shape, r, passes in gu.VALUES_LGA_CASES:
+        x, f, gy = pc.lga_inputs_exact(shape, r, sum(shape) + r)
+        y, ins = ref.lga_chain_forward(x, f, r, passes)
+        gx, gf = ref.lga_chain_backward(ins, f, gy, r)
+        out.update({f"{name}.x": x, f"{name}.f": f, f"{name}.gy": gy, f"{name}.y": y, f"{name}.gx": gx, f"{name}.gf": gf,
+                    f"{name}.meta": np.array([r, passes], np.int32)})
+    np.savez_compressed(os.path.join(HERE, "lga_values_golden.npz"), **out)
+    for fn in [f for f, _ in gu.VALUES_SGA_FILES] + ["lga_values_golden.npz"]:
+        print(fn, os.path.getsize(os.path.join(HERE, fn)), "bytes")
+
+
+def value_digests():
+    import json
+    ref = Oracle("reference")
+    fn = os.path.join(HERE, "digests.json")
+    with open(fn) as fh:
+        out = json.load(fh)
+    name, shape, seed = gu.SGA_SELECT_DIGEST
+    out[name] = {"shape": list(shape), "seed": seed, "family": "parity_cases.sga_inputs_select", "zeros": "-0 hashed as +0",
+                 "sha256": gu.sga_digests(ref, shape, seed, gu.sga_select_digest_inputs, canon=True)}
+    print(name, "done")
+    name, shape, seed = gu.LGA_EXACT_DIGEST
+    out[name] = {"shape": list(shape), "seed": seed, "family": "parity_cases.lga_inputs_exact", "zeros": "-0 hashed as +0",
+                 "sha256": gu.lga_digests(ref, shape, seed, gu.lga_exact_digest_inputs, canon=True)}
+    print(name, "done")
+    with open(fn, "w") as fh:
+        json.dump(out, fh, indent=1)
+        fh.write("\n")
+
+
 if __name__ == "__main__":
-    digests() if "--digests" in sys.argv else vs_ref() if "--vs-ref" in sys.argv else main()
+    (digests() if "--digests" in sys.argv else vs_ref() if "--vs-ref" in sys.argv else values() if "--values" in sys.argv
+     else value_digests() if "--value-digests" in sys.argv else main())

@@ -79,26 +79,65 @@ def lga_digest_inputs(shape, seed):
     return x, f, gy
 
 
-def sga_digests(ora, shape, seed):
-    """every array SgaFunction produces, forward and backward, as the oracle `ora` computes it -> {name: sha256}"""
-    x, gs, go = sga_digest_inputs(shape, seed)
+def sga_digests(ora, shape, seed, inputs=None, canon=False):
+    """every array SgaFunction produces, forward and backward, as the oracle `ora` computes it -> {name: sha256}
+    (`inputs`: another seeded input family; `canon`: float arrays hashed with -0 turned into +0, see canon_zero)"""
+    x, gs, go = (inputs or sga_digest_inputs)(shape, seed)
     d = {"in.x": sha(x), "in.go": sha(go), **{f"in.g{k}": sha(gs[k]) for k in range(4)}}
+    c = canon_zero if canon else (lambda a: a)
     out, tmp, mask = ora.sga_forward(x, *gs)
-    d.update({"out": sha(out), "temp_out": sha(tmp), "mask_u8": sha(mask.astype(np.uint8))})
+    d.update({"out": sha(c(out)), "temp_out": sha(c(tmp)), "mask_u8": sha(mask.astype(np.uint8))})
     for k in range(4):
-        d[f"A{k}"] = sha(ora.sga_scan(x, gs[k], k))
+        d[f"A{k}"] = sha(c(ora.sga_scan(x, gs[k], k)))
     for n, g in zip(("gx", "gw0", "gw1", "gw2", "gw3"), ora.sga_backward(x, *gs, tmp, mask, go)):
-        d[n] = sha(g)
+        d[n] = sha(c(g))
     return d
 
 
-def lga_digests(ora, shape, seed):
-    x, f, gy = lga_digest_inputs(shape, seed)
+def lga_digests(ora, shape, seed, inputs=None, canon=False):
+    x, f, gy = (inputs or lga_digest_inputs)(shape, seed)
     d = {"in.x": sha(x), "in.f": sha(f), "in.gy": sha(gy)}
     y, ins = ora.lga_chain_forward(x, f, 2, 2)
     gx, gf = ora.lga_chain_backward(ins, f, gy, 2)
-    d.update({"t1": sha(ins[1]), "y": sha(y), "gx": sha(gx), "gf": sha(gf)})
+    c = canon_zero if canon else (lambda a: a)
+    d.update({"t1": sha(c(ins[1])), "y": sha(c(y)), "gx": sha(c(gx)), "gf": sha(c(gf))})
     return d
+
+
+# ---- the value families (tests/parity_cases.py: sga_inputs_select / _dyadic / _sparse, lga_inputs_exact) pinned to the
+# reference: small fixtures (make_golden.py --values -> sga_values*_golden.npz, lga_values_golden.npz) and two full-size digest
+# entries (make_golden.py --value-digests, ADDED to digests.json).  On these two families every result is exactly
+# representable and so independent of the order of the sums: the GRADIENT digests hold for the device build too.
+VALUES_SGA_SHAPES = [("s33", (1, 2, 33, 8, 32)), ("s65", (1, 1, 65, 4, 48))]          # case name: f"{family}_{tag}"
+VALUES_SGA_FAMILIES = ["select", "dyadic", "sparse"]
+VALUES_SGA_FILES = [("sga_values_golden.npz", ("select", "dyadic")), ("sga_values_sparse_golden.npz", ("sparse",))]
+VALUES_LGA_CASES = [("exact_r2", (1, 9, 7, 12), 2, 2), ("exact_r3", (1, 12, 19, 33), 3, 1), ("exact_5d", (2, 3, 9, 5, 8), 2, 2)]
+SGA_SELECT_DIGEST = ("sga_cfg2_select", (1, 32, 65, 80, 208), 123)
+LGA_EXACT_DIGEST = ("lga2_cfg2_exact", (1, 193, 240, 624), 123)
+
+
+def canon_zero(a):
+    """-0 -> +0 (IEEE addition): a zero's sign depends on which zero product a sum starts from, and would change the hash"""
+    return np.asarray(a, np.float32) + np.float32(0)
+
+
+def values_sga_case_names():
+    return [f"{fam}_{tag}" for fam in VALUES_SGA_FAMILIES for tag, _ in VALUES_SGA_SHAPES]
+
+
+def load_values_sga(name):
+    """the fixture file that holds case `name` (f"{family}_{tag}")"""
+    return load(next(fn for fn, fams in VALUES_SGA_FILES if name.split("_")[0] in fams))
+
+
+def lga_exact_digest_inputs(shape, seed):
+    import parity_cases as pc
+    return pc.lga_inputs_exact(shape, 2, seed)
+
+
+def sga_select_digest_inputs(shape, seed):
+    import parity_cases as pc
+    return pc.sga_inputs_select(shape, seed)
 
 
 

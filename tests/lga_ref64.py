@@ -1,0 +1,109 @@
+"""A plain float64 numpy statement of LGA and its adjoints, written from the operation's definition (not from the oracle's C):
+
+    y[b, d, i, j] = sum over taps (dd, a, b') of f[b, t, i, j] * x[b, d+dd, i+a, j+b']
+                    dd in {-1, 0, 1}, a, b' in [-r, r], t = (dd+1) * K + (a+r) * (2r+1) + (b'+r), K = (2r+1)^2,
+
+where a tap whose index leaves the volume in depth, row or column reads the CENTRE value x[b, d, i, j] instead.
+4-D [B,D,H,W] with filters [B,3K,H,W], or 5-D [N,C,D,H,W] with filters [N,C,3K,H,W] (N*C folded)."""
+import numpy as np
+
+
+def _fold(x, f):
+    H, W = x.shape[-2:]
+    return x.reshape(-1, x.shape[-3], H, W).astype(np.float64), f.reshape(-1, f.shape[-3], H, W).astype(np.float64)
+
+
+def _taps(r, D, H, W):
+    """(tap index, dd, a, b, slices of the positions whose tap stays inside, slices of what they read)"""
+    ws = 2 * r + 1
+    for dd in (-1, 0, 1):
+        for a in range(-r, r + 1):
+            for b in range(-r, r + 1):
+                t = (dd + 1) * ws * ws + (a + r) * ws + (b + r)
+                dst, src = [], []
+                for off, n in ((dd, D), (a, H), (b, W)):
+                    lo, hi = max(0, -off), min(n, n - off)
+                    hi = max(hi, lo)
+                    dst.append(slice(lo, hi))
+                    src.append(slice(lo + off, hi + off))
+                yield t, tuple(dst), tuple(src)
+
+
+def lga_forward(x, f, r):
+    xs, fs = _fold(x, f)
+    B, D, H, W = xs.shape
+    y = np.zeros_like(xs)
+    for t, dst, src in _taps(r, D, H, W):
+        v = xs.copy()                                     # outside: the centre value
+        v[(slice(None),) + dst] = xs[(slice(None),) + src]
+        y += fs[:, t][:, None] * v
+    return y.reshape(x.shape)
+
+
+def lga_backward(x, f, gy, r):
+    """-> (gx, gf): the adjoints of lga_forward in x and in f"""
+    xs, fs = _fold(x, f)
+    gs = gy.reshape(xs.shape).astype(np.float64)
+    B, D, H, W = xs.shape
+    gx, gf = np.zeros_like(xs), np.zeros_like(fs)
+    for t, dst, src in _taps(r, D, H, W):
+        v = xs.copy()
+        v[(slice(None),) + dst] = xs[(slice(None),) + src]
+        gf[:, t] = (gs * v).sum(1)
+        c = fs[:, t][:, None] * gs                        # what each output position hands to the element it read
+        inside = np.zeros((D, H, W), bool)
+        inside[dst] = True
+        gx += np.where(inside, 0.0, c)                    # ... the centre, where the tap left the volume
+        gx[(slice(None),) + src] += c[(slice(None),) + dst]
+    return gx.reshape(x.shape), gf.reshape(f.shape)
+
+
+def lga_chain(x, f, gy, r, passes):
+    """`passes` chained passes with one filter tensor and their backward: -> dict(y, gx, gf, ins=[input of each pass])"""
+    ins = [np.asarray(x, np.float64)]
+    for _ in range(passes):
+        ins.append(lga_forward(ins[-1], f, r))
+    g, gf = np.asarray(gy, np.float64), 0.0
+    for xin in reversed(ins[:-1]):
+        g, gfk = lga_backward(xin, f, g, r)
+        gf = gf + gfk
+    return {"y": ins[-1], "gx": g, "gf": gf, "ins": ins[:-1]}
+
+
+def assert_lga_exact_by_norms(x, f, gy, r, passes):
+    """The same condition from norms alone, for volumes too large to push through the float64 chain: a forward pass
+    multiplies max|.| by at most F = max over pixels of sum_t |f_t|; a data-backward pass by at most S = 2 T max|f| (an
+    element is read through at most T taps of its neighbours, one each, and through at most T out-of-range taps of its
+    own pixel); a filter gradient is a sum over D products of an input and a gradient of its pass.  Grids: 1/8 per filter
+    factor (y, gx: `passes` factors; each term of gf: `passes` - 1)."""
+    for v in (x, gy, 8 * f):
+        assert np.array_equal(v, np.round(v))
+    T, D = f.shape[-3], x.shape[-3]
+    F = float(np.abs(f).sum(-3).max())
+    S = 2.0 * T * float(np.abs(f).max())
+    mx, mg = float(np.abs(x).max()), float(np.abs(gy).max())
+    ins = [mx * F ** k for k in range(passes)]                   # max|input of pass k|
+    gs = [mg * S ** k for k in range(passes)]                    # max|gradient of the output of pass (passes-1-k)|
+    bounds = {"y": mx * F ** passes * 8.0 ** passes, "gx": mg * S ** passes * 8.0 ** passes,
+              "gf": sum(D * ins[passes - 1 - k] * gs[k] for k in range(passes)) * 8.0 ** (passes - 1)}
+    assert max(bounds.values()) < 2 ** 24, bounds
+    return bounds
+
+
+def assert_lga_exact(x, f, gy, r, passes):
+    """Exactness condition of the exact LGA family: the float64 chain on the ABSOLUTE values of the inputs bounds every
+    partial sum of every result in any order; in units of the result's grid (filters are multiples of 1/8: 1/8 per filter
+    factor -- y and gx carry `passes` factors, gf up to `passes` - 1 and the data) it must stay below 2^24, the range
+    in which fp32 holds every multiple of the grid exactly.  -> the float64 results on the real inputs."""
+    for v in (x, gy, 8 * f):
+        assert np.array_equal(v, np.round(v))
+    bound = lga_chain(np.abs(x), np.abs(f), np.abs(gy), r, passes)
+    grid = 8.0 ** passes
+    for k in ("y", "gx", "gf"):
+        assert np.abs(bound[k]).max() * grid < 2 ** 24, (k, float(np.abs(bound[k]).max()), grid)
+    for v in bound["ins"]:
+        assert np.abs(v).max() * grid < 2 ** 24
+    want = lga_chain(x, f, gy, r, passes)
+    for k in ("y", "gx", "gf"):
+        assert np.array_equal(want[k], want[k].astype(np.float32).astype(np.float64)), k     # representable in fp32 at all
+    return want

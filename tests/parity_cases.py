@@ -24,6 +24,129 @@ def sga_inputs(shape, seed):
     return x, gs, go
 
 
+# ---- value families: inputs that make ties frequent and (select, lga exact) every partial sum exactly representable ----------
+_SELECT_P = (0.35, 0.2, 0.1, 0.1, 0.25)
+_DYADIC_PATTERNS = np.array([[1, 0, 0, 0, 0], [.5, .5, 0, 0, 0], [.5, 0, 0, 0, .5], [.5, .25, .25, 0, 0], [.25, .25, .25, 0, .25],
+                             [0, 0, 0, 0, 1], [0, 1, 0, 0, 0], [.5, 0, .25, .25, 0], [0, 0, 0, 0, 0]], np.float32)
+
+
+def sga_inputs_select(shape, seed):
+    """*selection* family: x, go integers in [-2, 2]; per (n, c, h, w) exactly one of the five guidance taps is 1.0.  Every
+    volume entry is then one of five values whatever the scanline length, every gradient an integer: ties everywhere, and
+    results that do not depend on summation order or contraction (equality with the oracle, gradients included)."""
+    rng = np.random.default_rng(seed)
+    N, C, D, H, W = shape
+    x = rng.integers(-2, 3, shape).astype(np.float32)
+    gs = []
+    for _ in range(4):
+        tap = rng.choice(5, size=(N, C, H, W), p=_SELECT_P)
+        g = np.zeros((N, C, 5, H, W), np.float32)
+        np.put_along_axis(g, tap[:, :, None], 1.0, axis=2)
+        gs.append(g)
+    go = rng.integers(-2, 3, shape).astype(np.float32)
+    return x, gs, go
+
+
+def sga_inputs_dyadic(shape, seed):
+    """per pixel one of nine dyadic tap patterns (|w|_1 <= 1, an all-zero one among them), each entry negated with probability
+    1/4; integer x, go.  Bounded, signed weights; ties that decay along the scanline.  Gradients are not exact here."""
+    rng = np.random.default_rng(seed)
+    N, C, D, H, W = shape
+    x = rng.integers(-2, 3, shape).astype(np.float32)
+    gs = []
+    for _ in range(4):
+        g = _DYADIC_PATTERNS[rng.integers(0, len(_DYADIC_PATTERNS), (N, C, H, W))]            # N C H W 5
+        sign = rng.choice(np.array([1, 1, 1, -1], np.float32), g.shape)
+        gs.append(np.ascontiguousarray(np.moveaxis(g * sign, -1, 2)))
+    go = rng.integers(-2, 3, shape).astype(np.float32)
+    return x, gs, go
+
+
+def sga_inputs_sparse(shape, seed):
+    """model-like: x = relu(randn) with the cost volume's wedge zeroed (x[..., d, :, w] = 0 for w < d); guidance = randn with
+    30 % of the taps exactly 0, L1-normalised (0 where the norm is 0), 10 % of the pixels zeroed entirely; go = randn."""
+    rng = np.random.default_rng(seed)
+    N, C, D, H, W = shape
+    x = np.maximum(rng.standard_normal(shape), 0).astype(np.float32)
+    wedge = np.arange(W)[None, :] < np.arange(D)[:, None]                                      # D W
+    x[np.broadcast_to(wedge[None, None, :, None, :], shape)] = 0
+    gs = []
+    for _ in range(4):
+        g = rng.standard_normal((N, C, 5, H, W)) * (rng.random((N, C, 5, H, W)) > 0.3)
+        s = np.abs(g).sum(2, keepdims=True)
+        g = np.where(s > 0, g / np.maximum(s, 1e-12), 0)
+        g = g * (rng.random((N, C, 1, H, W)) > 0.1)
+        gs.append(g.astype(np.float32))
+    go = rng.standard_normal(shape).astype(np.float32)
+    return x, gs, go
+
+
+SGA_FAMILIES = {"select": sga_inputs_select, "dyadic": sga_inputs_dyadic, "sparse": sga_inputs_sparse}
+# floors of (elements with a direction tie, pixels with an arg-max tie in each direction, pixels whose first arg-max is > 0),
+# for D >= 6 and at least 35 pixels per slice; set well under what the families give (select 0.55-0.74 / 0.50-1.0 / 0.41-0.65,
+# dyadic 0.13-0.21 / 0.46-0.87, sparse 0.07-0.21 / 0.18-0.41)
+SGA_TIE_FLOORS = {"select": (0.30, 0.30, 0.30), "dyadic": (0.05, 0.30, None), "sparse": (0.03, 0.10, None)}
+
+
+def sga_tie_stats(A):
+    """A: the four directional volumes [N,C,D,H,W] -> (fraction of elements where two or more directions share the maximum,
+    [per direction: fraction of pixels whose maximum over depth is attained more than once],
+    fraction of all (direction, pixel) pairs whose first arg-max is not disparity 0)"""
+    S = np.stack(A)
+    dir_ties = float(((S == S.max(0)).sum(0) > 1).mean())
+    am = [float(((a == a.max(2, keepdims=True)).sum(2) > 1).mean()) for a in A]
+    nz = float(np.mean([(np.argmax(a, 2) > 0).mean() for a in A]))
+    return dir_ties, am, nz
+
+
+def assert_sga_ties(family, A):
+    """the family's floors hold for these volumes (so that a test on them cannot pass vacuously)"""
+    dir_ties, am, nz = sga_tie_stats(A)
+    f_dir, f_am, f_nz = SGA_TIE_FLOORS[family]
+    assert dir_ties >= f_dir, (family, "direction ties", dir_ties)
+    assert min(am) >= f_am, (family, "arg-max ties", am)
+    assert f_nz is None or nz >= f_nz, (family, "first arg-max > 0", nz)
+    return dir_ties, am, nz
+
+
+def lga_inputs_exact(shape, r, seed):
+    """x, gy: integers in [-4, 4]; filters: integers in [-4, 4] / 8 with 40 % exactly 0, not normalised: every product and
+    partial sum of one to three passes is a multiple of 1/8, 1/64, 1/512 below 2^24 of them (lga_ref64.assert_lga_exact)."""
+    rng = np.random.default_rng(seed)
+    fs = list(shape)
+    fs[-3] = 3 * (2 * r + 1) ** 2
+    x = rng.integers(-4, 5, shape).astype(np.float32)
+    f = (rng.integers(-4, 5, fs) * (rng.random(fs) > 0.4)).astype(np.float32) / 8
+    gy = rng.integers(-4, 5, shape).astype(np.float32)
+    return x, f, gy
+
+
+def oracle_sga_want(oracle, x, gs, go):
+    """everything check_sga_forward_backward / check_sga_compat compare with, from the oracle (A0..A3 included)"""
+    out, tmp, mask = oracle.sga_forward(x, *gs)
+    grads = oracle.sga_backward(x, *gs, tmp, mask, go)
+    want = {"out": out, "mask": mask.astype(np.uint8), "tmp": tmp, "gx": grads[0]}
+    for d in range(4):
+        want[f"gw{d}"] = grads[1 + d]
+        want[f"A{d}"] = oracle.sga_scan(x, gs[d], d)
+    return want
+
+
+def assert_select_exact(x, gs, go):
+    """Exactness condition of the *select* family, whatever the routing of the gradient (mask, arg-max) and the order of the
+    sums.  With one tap of 1.0 per pixel every forward entry is a copy of an x entry (|A| <= max|x|), and the adjoint scan
+    hands each element's gradient to exactly one predecessor: gradient mass is merged (tap 4 collects a whole depth column
+    in its arg-max) but never duplicated.  So the absolute partial sums of any adjoint entry stay within
+    M = scanline length * max over pixels of sum_d |go|; those of gX within 4 M (four directions), those of a guidance
+    gradient (sum over d of adjoint * x or * A) within max|x| * M.  All are integers: exact in fp32 below 2^24."""
+    assert all(np.array_equal(g, np.round(g)) and np.array_equal(g.sum(2), np.ones_like(g[:, :, 0])) and g.min() == 0 for g in gs)
+    assert np.array_equal(x, np.round(x)) and np.array_equal(go, np.round(go))
+    M = max(x.shape[3], x.shape[4]) * float(np.abs(go).sum(2).max())
+    bound = 4 * M * max(1.0, float(np.abs(x).max()))
+    assert bound < 2 ** 24, bound
+    return bound
+
+
 _PAGE = mmap.PAGESIZE
 _libc = ctypes.CDLL(None, use_errno=True)
 _libc.mprotect.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]

@@ -314,3 +314,113 @@ def test_sgablock_residual_tail_in_place_and_no_grad(torch_mod):
     assert float((w.grad - w2.grad).abs().max()) <= 1e-5 and float((rem.grad - rem2.grad).abs().max()) == 0.0
     with pytest.raises(RuntimeError):
         ResidualBnRelu(bn)(t.cpu(), rem.detach().cpu())        # no CPU path
+
+
+# ---- stale BatchNorm folds, all-zero guidance ---------------------------------------------------------------------------------
+
+def test_fused_bn_modules_follow_statistics_updated_by_a_train_mode_forward(torch_mod):
+    """GuidedSGABnRelu and ResidualBnRelu, eval -> train-mode forward (no optimizer step) -> eval under no_grad, against the
+    unfused op chain on the same device.  A train-mode batch_norm moves running_mean / running_var without bumping their
+    version counters; the fold kept on the module (folded_bn) must not survive that."""
+    torch = torch_mod
+    from ganet_amd.functions.fused import normalize_guidance
+    from ganet_amd.functions.GANet import SgaFunction
+    from ganet_amd.modules.fused import GuidedSGABnRelu, ResidualBnRelu
+    torch.manual_seed(21)
+    N, C, D, H, W = 1, 4, 17, 8, 24
+    x = torch.randn(N, C, D, H, W, device="cuda")
+    g = torch.randn(N, 20 * C, H, W, device="cuda")
+    rem = torch.randn(N, C, D, H, W, device="cuda")
+    shifted = 3.0 * torch.randn(2, C, D, H, W, device="cuda") + 2.0           # what the train-mode forwards see
+    for make in ("sga", "tail"):
+        bn = _bn3d(torch, C, 6).cuda()
+        for p in bn.parameters():
+            p.requires_grad_(False)
+        m = (GuidedSGABnRelu(bn) if make == "sga" else ResidualBnRelu(bn, inplace=False)).eval()
+
+        def fused():
+            with torch.no_grad():
+                return m(x, g) if make == "sga" else m(x, rem)
+
+        def chain():
+            with torch.no_grad():
+                if make == "sga":
+                    return torch.relu(bn(SgaFunction.apply(x, *normalize_guidance(g, C))))
+                return torch.relu(bn(x) + rem)
+
+        first = fused()
+        assert float((first - chain()).abs().max()) <= 1e-5 * max(1.0, float(first.abs().max()))
+        mean_before = bn.running_mean.clone()
+        m.train()
+        bn(shifted)                                   # statistics move; no optimizer step, no version bump of the buffers
+        if make == "tail":
+            m(shifted[:1], rem)                       # ... and once through the module's own training path
+        m.eval()
+        assert float((bn.running_mean - mean_before).abs().max()) > 0.05
+        second, want = fused(), chain()
+        assert float((second - want).abs().max()) <= 1e-5 * max(1.0, float(want.abs().max())), \
+            (make, float((second - want).abs().max()))
+        assert float((second - first).abs().max()) > 1e-2, "the outputs must have moved with the statistics"
+
+
+def test_normalize_with_all_zero_groups_and_exact_zero_taps(torch_mod, port_oracle):
+    """F.normalize(p=1) divides by max(norm, 1e-12): an all-zero group stays all zero (no 0/0), exact-zero taps stay exactly
+    zero.  normalize_guidance / normalize_filters on such inputs against torch, forward and backward, and GuidedSGA on such
+    guidance against the oracle (pixels without any guidance: the volumes there are exactly 0 in every direction)."""
+    torch = torch_mod
+    import torch.nn.functional as F
+    from ganet_amd.functions.fused import normalize_filters, normalize_guidance
+    from ganet_amd.modules.fused import GuidedSGA
+    gen = torch.Generator().manual_seed(31)
+    N, C, D, H, W = 2, 3, 17, 9, 16
+    g = torch.randn(N, 20 * C, H, W, generator=gen)
+    g = g * (torch.rand(g.shape, generator=gen) > 0.3)                                     # exact-zero taps
+    dead = (torch.rand(N, 4 * C, 1, H, W, generator=gen) < 0.15)                           # whole groups of five
+    g = (g.view(N, 4 * C, 5, H, W) * ~dead).view(N, 20 * C, H, W).contiguous()
+    assert int(dead.sum()) > 50
+    gd = g.cuda().requires_grad_()
+    ks = normalize_guidance(gd, C)
+    gc = g.clone().requires_grad_()
+    kc = fr.sgablock_guidance(gc, C)
+    gks = [torch.randn(k.shape, generator=gen) for k in kc]
+    torch.autograd.backward(ks, [t.cuda() for t in gks])
+    torch.autograd.backward(kc, gks)
+    for a, b in zip(ks, kc):
+        an, bn_ = _np(a), _np(b)
+        assert np.isfinite(an).all()
+        assert np.array_equal(an == 0, bn_ == 0), "zeros must stay exactly zero, and nothing else become zero"
+        np.testing.assert_allclose(an, bn_, rtol=1e-5, atol=0)
+    assert np.isfinite(_np(gd.grad)).all()
+    np.testing.assert_allclose(_np(gd.grad), gc.grad.numpy(), rtol=1e-4, atol=1e-5)
+
+    f = torch.randn(2, 75, 7, 12, generator=gen) * (torch.rand(2, 75, 7, 12, generator=gen) > 0.4)
+    f = (f * (torch.rand(2, 1, 7, 12, generator=gen) > 0.2)).contiguous()                  # pixels without any filter
+    fd = f.cuda().requires_grad_()
+    y = normalize_filters(fd)
+    fc = f.clone().requires_grad_()
+    w = F.normalize(fc, p=1, dim=1)
+    gy = torch.randn(f.shape, generator=gen)
+    y.backward(gy.cuda())
+    w.backward(gy)
+    assert np.array_equal(_np(y) == 0, _np(w) == 0) and np.isfinite(_np(y)).all()
+    np.testing.assert_allclose(_np(y), _np(w), rtol=1e-5, atol=0)
+    np.testing.assert_allclose(_np(fd.grad), fc.grad.numpy(), rtol=1e-4, atol=1e-5)
+
+    x = torch.randn(N, C, D, H, W, generator=gen).cuda().requires_grad_()
+    go = torch.randn(N, C, D, H, W, generator=gen).cuda()
+    gd.grad = None
+    out = GuidedSGA()(x, gd)
+    out.backward(go)
+    torch.cuda.synchronize()
+    kn = [np.ascontiguousarray(_np(k)) for k in ks]                                         # the device's own normalised taps
+    o_out, o_tmp, o_mask = port_oracle.sga_forward(_np(x), *kn)
+    o_g = port_oracle.sga_backward(_np(x), *kn, o_tmp, o_mask, _np(go))
+    assert np.array_equal(_np(out), o_out), "same taps, same fma order: the forward is bit-exact"
+    assert np.abs(_np(x.grad) - o_g[0]).max() <= pc.TOL
+    gc.grad = None
+    torch.autograd.backward(fr.sgablock_guidance(gc, C), [torch.from_numpy(np.ascontiguousarray(a)) for a in o_g[1:]])
+    # (an all-zero group's gradient is the tap gradient / 1e-12, as in torch: 1e-4 on the tap gradient is 1e8 there -- finite,
+    # and compared above on given gradients; the bar of the op holds on the groups that carry guidance)
+    live = (g.view(N, 4 * C, 5, H, W).abs().sum(2, keepdim=True) > 0).expand(N, 4 * C, 5, H, W).reshape(N, 20 * C, H, W).numpy()
+    assert np.isfinite(_np(gd.grad)).all()
+    assert np.abs(_np(gd.grad) - gc.grad.numpy())[live].max() <= pc.TOL

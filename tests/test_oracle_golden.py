@@ -98,3 +98,76 @@ def test_lga2_full_size_restatement_matches_reference_digests(port_oracle, name,
     want = gu.load_digests()[name]
     got = gu.lga_digests(port_oracle, shape, seed)
     assert got == want["sha256"], [k for k in got if got[k] != want["sha256"][k]]
+
+
+# ---- the value families (tie-heavy / exactly representable inputs, tests/parity_cases.py) pinned to the reference -------------
+@pytest.mark.parametrize("name", gu.values_sga_case_names())
+def test_sga_value_families_match_golden(port_oracle, name):
+    """select / dyadic / sparse on (1,2,33,8,32) and (1,1,65,4,48): the restatement against every output of the reference's
+    kernel bodies, bit for bit; the stored inputs are what the seeded family gives today."""
+    import parity_cases as pc
+    z = gu.load_values_sga(name)
+    x, go = z[f"{name}.x"], z[f"{name}.go"]
+    gs = [z[f"{name}.g{d}"] for d in range(4)]
+    x2, gs2, go2 = pc.SGA_FAMILIES[name.split("_")[0]](x.shape, sum(x.shape))
+    assert np.array_equal(x, x2) and np.array_equal(go, go2) and all(np.array_equal(a, b) for a, b in zip(gs, gs2))
+    out, tmp, mask = port_oracle.sga_forward(x, *gs)
+    assert_bit_equal(out, z[f"{name}.out"], "out")
+    assert_bit_equal(tmp, z[f"{name}.tmp"], "temp_out")
+    assert np.array_equal(mask.astype(np.uint8), z[f"{name}.mask"])
+    for d in range(4):
+        assert_bit_equal(port_oracle.sga_scan(x, gs[d], d), z[f"{name}.A{d}"], f"A{d}")
+    grads = port_oracle.sga_backward(x, *gs, tmp, mask, go)
+    assert_bit_equal(grads[0], z[f"{name}.gx"], "gradInput")
+    for d in range(4):
+        assert_bit_equal(grads[1 + d], z[f"{name}.gw{d}"], f"grad{d}")
+
+
+@pytest.mark.parametrize("name", gu.values_sga_case_names())
+def test_sga_value_fixtures_really_have_ties(name):
+    """the floors of parity_cases.SGA_TIE_FLOORS on the REFERENCE's volumes: direction ties, arg-max ties in each direction,
+    and (select) first arg-max positions other than disparity 0"""
+    import parity_cases as pc
+    z = gu.load_values_sga(name)
+    pc.assert_sga_ties(name.split("_")[0], [z[f"{name}.A{d}"] for d in range(4)])
+
+
+@pytest.mark.parametrize("name", [c[0] for c in gu.VALUES_LGA_CASES])
+def test_lga_exact_family_matches_golden_and_float64(port_oracle, name):
+    """the exact LGA family: restatement == reference bit for bit, and both == the float64 statement of the operation"""
+    import lga_ref64
+    z = load("lga_values_golden.npz")
+    r, passes = (int(v) for v in z[f"{name}.meta"])
+    x, f, gy = z[f"{name}.x"], z[f"{name}.f"], z[f"{name}.gy"]
+    y, ins = port_oracle.lga_chain_forward(x, f, r, passes)
+    gx, gf = port_oracle.lga_chain_backward(ins, f, gy, r)
+    w64 = lga_ref64.assert_lga_exact(x, f, gy, r, passes)
+    for k, v in (("y", y), ("gx", gx), ("gf", gf)):
+        assert_bit_equal(v, z[f"{name}.{k}"], k)
+        assert np.array_equal(z[f"{name}.{k}"].astype(np.float64), w64[k]), k
+
+
+def test_sga_select_full_size_restatement_matches_reference_digests(port_oracle):
+    """the *select* family at [1,32,65,80,208]: every array of forward AND backward (order-independent here, so the same
+    digests hold for the device build: tests/test_gpu_values.py); tie floors and exactness condition at this size."""
+    import parity_cases as pc
+    name, shape, seed = gu.SGA_SELECT_DIGEST
+    want = gu.load_digests()[name]
+    assert tuple(want["shape"]) == shape and want["seed"] == seed
+    x, gs, go = pc.sga_inputs_select(shape, seed)
+    pc.assert_select_exact(x, gs, go)
+    pc.assert_sga_ties("select", [port_oracle.sga_scan(x, gs[d], d) for d in range(4)])
+    got = gu.sga_digests(port_oracle, shape, seed, gu.sga_select_digest_inputs, canon=True)
+    assert got == want["sha256"], [k for k in got if got[k] != want["sha256"][k]]
+
+
+def test_lga2_exact_full_size_restatement_matches_reference_digests(port_oracle):
+    """the exact LGA family at [1,193,240,624], Lga2Function: intermediate, output, both gradients"""
+    import lga_ref64
+    import parity_cases as pc
+    name, shape, seed = gu.LGA_EXACT_DIGEST
+    want = gu.load_digests()[name]
+    assert tuple(want["shape"]) == shape and want["seed"] == seed
+    lga_ref64.assert_lga_exact_by_norms(*pc.lga_inputs_exact(shape, 2, seed), 2, 2)
+    got = gu.lga_digests(port_oracle, shape, seed, gu.lga_exact_digest_inputs, canon=True)
+    assert got == want["sha256"], [k for k in got if got[k] != want["sha256"][k]]

@@ -96,6 +96,31 @@ def test_filter_normalize_any_K(sim, K):
     np.testing.assert_allclose(gx, tg.grad.numpy(), rtol=1e-4, atol=1e-5)
 
 
+@pytest.mark.parametrize("K", [75, 5])
+def test_filter_normalize_with_all_zero_pixels_and_exact_zero_taps(sim, K):
+    """pixels without any filter (norm clamped to 1e-12: all zero out, gradient gy / 1e-12) and exact-zero taps (sgn(0) = 0,
+    the tap stays exactly 0) on the run-time-K walk (K = 75) and the register form (K = 5), against F.normalize(p=1)"""
+    rng = np.random.default_rng(K + 1)
+    N, H, W = 2, 5, 6
+    g = (rng.standard_normal((N, K, H, W)) * (rng.random((N, K, H, W)) > 0.4) * (rng.random((N, 1, H, W)) > 0.25)).astype(np.float32)
+    assert (np.abs(g).sum(1) == 0).sum() >= 5 and (g == 0).mean() > 0.4
+    gy = rng.standard_normal((N, K, H, W)).astype(np.float32)
+    y = np.full_like(g, np.nan)
+    _call(sim, "ganet_l1_normalize_forward", _p(g), _p(y), None, None, None, N, 1, 1, K, H, W, None)
+    tg = torch.from_numpy(g).requires_grad_()
+    want = fr.lga_filters(tg)
+    assert np.array_equal(y == 0, g == 0)
+    np.testing.assert_allclose(y, want.detach().numpy(), rtol=RTOL, atol=ATOL)
+    want.backward(torch.from_numpy(gy))
+    gx = np.full_like(g, np.nan)
+    _call(sim, "ganet_l1_normalize_backward", _p(g), _p(gy), None, None, None, _p(gx), N, 1, 1, K, H, W, None)
+    wg = tg.grad.numpy()
+    ok = np.abs(wg) < 1e6
+    assert (~ok).sum() >= 5 * K // 2
+    np.testing.assert_allclose(gx[ok], wg[ok], rtol=1e-4, atol=1e-5)
+    np.testing.assert_allclose(gx[~ok], wg[~ok], rtol=1e-4)
+
+
 @pytest.mark.parametrize("N,maxdisp,H,W", [(1, 8, 3, 5), (2, 23, 4, 4), (1, 192, 2, 3)])
 def test_norm_disparity_regression(sim, N, maxdisp, H, W):
     rng = np.random.default_rng(maxdisp)
