@@ -71,23 +71,23 @@ def test_normalize_functions_match_torch(torch_mod):
     np.testing.assert_allclose(_np(g2.grad), g2c.grad.numpy(), rtol=1e-4, atol=1e-6)
 
 
-@pytest.mark.parametrize("maxdisp,H,W", [(11, 14, 36), (192, 24, 624)])
-def test_dispagg_tail_matches_reference_statements(torch_mod, port_oracle, maxdisp, H, W):
-    """DispAggTail == models/GANet_deep.py:243-247, forward and all three gradients: a small volume (maxdisp 11) and a
-    full-width strip at the models' maxdisp 192 ([1,193,24,624])."""
-    torch = torch_mod
+def _dispagg_tail_case(torch, port_oracle, maxdisp, H, W, radius=2):
+    """DispAggTail(maxdisp, radius) against oracle/fused_ref.dispagg_tail: forward and all three gradients.  The fused last
+    pass (ganet_lga_forward_regress) exists for radius 1 and 2; radius 3 answers E_UNSUPPORTED and LgaRegressFunction runs the
+    plain pass followed by ganet_norm_disparity_regression_forward -- the two sums are then taken from those entries."""
     from ganet_amd.modules.fused import DispAggTail
+    K = 3 * (2 * radius + 1) ** 2
     torch.manual_seed(3)
     x = torch.randn(1, maxdisp + 1, H, W, device="cuda", requires_grad=True)
-    lg1 = torch.randn(1, 75, H, W, device="cuda", requires_grad=True)
-    lg2 = torch.randn(1, 75, H, W, device="cuda", requires_grad=True)
+    lg1 = torch.randn(1, K, H, W, device="cuda", requires_grad=True)
+    lg2 = torch.randn(1, K, H, W, device="cuda", requires_grad=True)
     go = torch.randn(1, H, W, device="cuda")
-    out = DispAggTail(maxdisp)(x, lg1, lg2)
+    out = DispAggTail(maxdisp, radius)(x, lg1, lg2)
     out.backward(go)
     torch.cuda.synchronize()
     xc, l1c, l2c = (t.detach().cpu().requires_grad_() for t in (x, lg1, lg2))
     parts = {}
-    want = fr.dispagg_tail(xc, l1c, l2c, maxdisp, port_oracle, parts=parts)
+    want = fr.dispagg_tail(xc, l1c, l2c, maxdisp, port_oracle, radius=radius, parts=parts)
     want.backward(go.cpu())
     # The tail ends in out = S_dy / S_abs with S_dy = sum_d d * y[d], S_abs = sum_d |y[d]| of the SIGNED second LGA output: where
     # S_abs is tiny the division amplifies fp32 rounding.  So the two sums are held to north_star's 1e-4 on their own (S_dy
@@ -98,10 +98,23 @@ def test_dispagg_tail_matches_reference_statements(torch_mod, port_oracle, maxdi
     from ganet_amd.functions.fused import SoftminFunction, normalize_filters
     from ganet_amd.modules.fused import NormalizedLGA2
     with torch.no_grad():
-        x2 = LgaFunction.apply(SoftminFunction.apply(NormalizedLGA2(2)(x, lg1).contiguous()), normalize_filters(lg2), 2)
+        x2 = LgaFunction.apply(SoftminFunction.apply(NormalizedLGA2(radius)(x, lg1).contiguous()), normalize_filters(lg2), radius)
+        f2 = normalize_filters(lg2)
         s_abs, s_dy = torch.empty(1, H, W, device="cuda"), torch.empty(1, H, W, device="cuda")
-        _native.lib().call("ganet_lga_forward_regress", x2.data_ptr(), normalize_filters(lg2).data_ptr(), None, s_abs.data_ptr(),
-                           s_dy.data_ptr(), 1, maxdisp + 1, H, W, 2, torch.cuda.current_stream().cuda_stream)
+        stream = torch.cuda.current_stream().cuda_stream
+        if radius <= 2:
+            _native.lib().call("ganet_lga_forward_regress", x2.data_ptr(), f2.data_ptr(), None, s_abs.data_ptr(),
+                               s_dy.data_ptr(), 1, maxdisp + 1, H, W, radius, stream)
+        else:
+            with pytest.raises(_native.GanetError) as unsupported:
+                _native.lib().call("ganet_lga_forward_regress", x2.data_ptr(), f2.data_ptr(), None, s_abs.data_ptr(),
+                                   s_dy.data_ptr(), 1, maxdisp + 1, H, W, radius, stream)
+            assert unsupported.value.code == _native.E_UNSUPPORTED, "DispAggTail must have taken LgaRegressFunction's fallback"
+            y3, q = torch.empty_like(x2), torch.empty(1, H, W, device="cuda")
+            _native.lib().call("ganet_lga_forward", x2.data_ptr(), f2.data_ptr(), y3.data_ptr(), 1, maxdisp + 1, H, W, radius, stream)
+            _native.lib().call("ganet_norm_disparity_regression_forward", y3.data_ptr(), q.data_ptr(), s_abs.data_ptr(), 1,
+                               maxdisp + 1, H, W, stream)
+            _native.lib().call("ganet_disparity_regression_forward", y3.data_ptr(), s_dy.data_ptr(), 1, maxdisp + 1, H, W, stream)
         torch.cuda.synchronize()
     y2 = parts["y2"].numpy().astype(np.float64)
     ref_abs = np.abs(y2).sum(1)
@@ -121,6 +134,42 @@ def test_dispagg_tail_matches_reference_statements(torch_mod, port_oracle, maxdi
     for got, ref in ((x.grad, xc.grad), (lg1.grad, l1c.grad), (lg2.grad, l2c.grad)):
         scale = max(1.0, float(np.abs(ref.numpy()).max()))
         assert np.abs(_np(got) - ref.numpy()).max() <= pc.TOL * scale, (np.abs(_np(got) - ref.numpy()).max(), scale)
+
+
+@pytest.mark.parametrize("maxdisp,H,W", [(11, 14, 36), (192, 24, 624)])
+def test_dispagg_tail_matches_reference_statements(torch_mod, port_oracle, maxdisp, H, W):
+    """DispAggTail == models/GANet_deep.py:243-247, forward and all three gradients: a small volume (maxdisp 11) and a
+    full-width strip at the models' maxdisp 192 ([1,193,24,624])."""
+    _dispagg_tail_case(torch_mod, port_oracle, maxdisp, H, W)
+
+
+@pytest.mark.parametrize("radius", [1, 3])
+def test_dispagg_tail_radius_1_and_3(torch_mod, port_oracle, radius):
+    """[1,12,14,36] with filters [1, 3(2r+1)^2, 14, 36]: radius 1 ends in lga_apply_pp<1, false, true>, radius 3 in
+    LgaRegressFunction's E_UNSUPPORTED fallback (asserted inside) -- same assertions as at radius 2."""
+    _dispagg_tail_case(torch_mod, port_oracle, 11, 14, 36, radius=radius)
+
+
+@pytest.mark.parametrize("radius", [1, 2, 3])
+def test_dispagg_tail_no_grad_equals_autograd_output(torch_mod, radius):
+    """under no_grad the last pass writes no volume (radius 1, 2) resp. keeps nothing (radius 3): the disparities are the
+    autograd-enabled ones bit for bit"""
+    torch = torch_mod
+    from ganet_amd.modules.fused import DispAggTail
+    maxdisp, H, W = 11, 14, 36
+    K = 3 * (2 * radius + 1) ** 2
+    torch.manual_seed(4 + radius)
+    x = torch.randn(1, maxdisp + 1, H, W, device="cuda", requires_grad=True)
+    lg1 = torch.randn(1, K, H, W, device="cuda", requires_grad=True)
+    lg2 = torch.randn(1, K, H, W, device="cuda", requires_grad=True)
+    m = DispAggTail(maxdisp, radius)
+    with_grad = m(x, lg1, lg2)
+    assert with_grad.requires_grad
+    with torch.no_grad():
+        without = m(x, lg1, lg2)
+    torch.cuda.synchronize()
+    assert not without.requires_grad and np.isfinite(_np(without)).all()
+    assert np.array_equal(_np(with_grad).view(np.uint32), _np(without).view(np.uint32))
 
 
 def test_norm_regression_full_size(torch_mod):
