@@ -11,7 +11,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libganet_hip.so"
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -58,6 +58,9 @@ _PROTOS = {
     "ganet_trilinear_upsample_backward": [_P] * 2 + [_I] * 7 + [_P],
     "ganet_residual_relu_forward": [_P] * 5 + [_I] * 5 + [_P],
     "ganet_residual_relu_backward": [_P] * 5 + [_I] * 5 + [_P],
+    "ganet_disparity_loss_workspace": [_I] * 3,
+    "ganet_disparity_loss_forward": [_P] * 8 + [_I] * 8 + [_P],
+    "ganet_disparity_loss_backward": [_P] * 10 + [_I] * 8 + [_P],
     "ganet_selftest_dpp": [_P, _P, _P],
     "ganet_selftest_dpp_wave": [_P, _P, _P],
 }

@@ -3,6 +3,7 @@
 // Compiled by hipcc for gfx950 (product) and by g++ -DGA_HIPSIM (CPU test emulator).
 #include "ga_common.h"
 #include "lga_kernels.h"
+#include "loss_kernels.h"
 #include "misc_kernels.h"
 #include "sga_kernels.h"
 #include "sga_row_kernels.h"
@@ -1452,6 +1453,80 @@ GA_EXPORT int ganet_residual_relu_backward(const float *y, const float *grad_y, 
   else
     GA_LAUNCH((residual_relu_bwd<false>), residual_grid(S, slice), dim3(256), st, y, grad_y, bn_scale, grad_t, grad_rem, S, C, slice);
   return check_launch("residual + relu backward");
+}
+
+// ---- the training criterion and its error read-out (train.py:100-126, evaluation.py:199-202) --------------
+namespace {
+int check_loss(const char *who, const float *const *p, const float *target, const float *params, int N, int H, int W, int P,
+               const int *kind, int mask_mode)
+{
+  if (N <= 0 || H <= 0 || W <= 0) return fail(GANET_E_INVALID, "%s: non-positive size N=%d H=%d W=%d", who, N, H, W);
+  if (P < 1 || P > 3) return fail(GANET_E_INVALID, "%s: P=%d, 1 <= P <= 3", who, P);
+  if (mask_mode != 0 && mask_mode != 1) return fail(GANET_E_INVALID, "%s: mask_mode=%d (0: t < hi, 1: lo <= t <= hi)", who, mask_mode);
+  if (!target || !params) return fail(GANET_E_INVALID, "%s: null pointer", who);
+  for (int k = 0; k < P; k++) {
+    if (!p[k]) return fail(GANET_E_INVALID, "%s: null prediction %d", who, k);
+    if (kind[k] != 0 && kind[k] != 1) return fail(GANET_E_INVALID, "%s: kind%d=%d (0: smooth-L1, 1: MyLoss2)", who, k, kind[k]);
+  }
+  if ((i64)N * H * W >= (1 << 24))
+    return fail(GANET_E_UNSUPPORTED, "%s: %lld pixels; counts are reported as floats, which holds below 2^24", who, (long long)N * H * W);
+  return GANET_OK;
+}
+}  // namespace
+
+GA_EXPORT int ganet_disparity_loss_workspace(int N, int H, int W)
+{
+  if (N <= 0 || H <= 0 || W <= 0) return fail(GANET_E_INVALID, "ganet_disparity_loss_workspace: non-positive size");
+  if ((i64)N * H * W >= (1 << 24)) return fail(GANET_E_UNSUPPORTED, "ganet_disparity_loss_workspace: 2^24 pixels or more");
+  return LOSS_MAX_BLOCKS * LOSS_ROW;
+}
+
+GA_EXPORT int ganet_disparity_loss_forward(const float *p0, const float *p1, const float *p2, const float *target,
+                                           const float *params, double *workspace, float *loss, float *stats, int N, int H,
+                                           int W, int P, int kind0, int kind1, int kind2, int mask_mode, void *stream)
+{
+  const float *ps[3] = {p0, p1, p2};
+  const int kinds[3] = {kind0, kind1, kind2};
+  GA_TRY(check_loss("ganet_disparity_loss_forward", ps, target, params, N, H, W, P, kinds, mask_mode));
+  if (!workspace || !loss || !stats) return fail(GANET_E_INVALID, "ganet_disparity_loss_forward: null pointer");
+  LossMaps m = {};
+  bool vec = aligned16(target);
+  for (int k = 0; k < P; k++) { m.p[k] = ps[k]; m.kind[k] = kinds[k]; vec = vec && aligned16(ps[k]); }
+  const i64 total = (i64)N * H * W;
+  vec = vec && total % 4 == 0;
+  const i64 want = ((vec ? total / 4 : total) + LOSS_BLOCK - 1) / LOSS_BLOCK;
+  const int rows = (int)(want < LOSS_MAX_BLOCKS ? want : LOSS_MAX_BLOCKS);
+  hipStream_t st = (hipStream_t)stream;
+  if (vec) GA_LAUNCH((loss_partials<4>), dim3(rows), dim3(LOSS_BLOCK), st, m, target, params, workspace, total, P, mask_mode);
+  else GA_LAUNCH((loss_partials<1>), dim3(rows), dim3(LOSS_BLOCK), st, m, target, params, workspace, total, P, mask_mode);
+  GA_TRY(check_launch("disparity loss partial sums"));
+  GA_LAUNCH(loss_finish, dim3(1), dim3(64), st, workspace, rows, params, P, loss, stats);
+  return check_launch("disparity loss finish");
+}
+
+GA_EXPORT int ganet_disparity_loss_backward(const float *p0, const float *p1, const float *p2, const float *target,
+                                            const float *params, const float *stats, const float *grad_loss, float *g0,
+                                            float *g1, float *g2, int N, int H, int W, int P, int kind0, int kind1, int kind2,
+                                            int mask_mode, void *stream)
+{
+  const float *ps[3] = {p0, p1, p2};
+  float *gs[3] = {g0, g1, g2};
+  const int kinds[3] = {kind0, kind1, kind2};
+  GA_TRY(check_loss("ganet_disparity_loss_backward", ps, target, params, N, H, W, P, kinds, mask_mode));
+  if (!stats || !grad_loss) return fail(GANET_E_INVALID, "ganet_disparity_loss_backward: null pointer");
+  LossMaps m = {};
+  bool vec = aligned16(target), any = false;
+  for (int k = 0; k < P; k++) {
+    m.p[k] = ps[k]; m.g[k] = gs[k]; m.kind[k] = kinds[k];
+    if (gs[k]) { any = true; vec = vec && aligned16(ps[k]) && aligned16(gs[k]); }
+  }
+  if (!any) return GANET_OK;
+  const i64 total = (i64)N * H * W;
+  vec = vec && total % 4 == 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (vec) GA_LAUNCH((loss_bwd<4>), dim3(ew_grid(total / 4)), dim3(256), st, m, target, params, stats, grad_loss, total, P, mask_mode);
+  else GA_LAUNCH((loss_bwd<1>), dim3(ew_grid(total)), dim3(256), st, m, target, params, stats, grad_loss, total, P, mask_mode);
+  return check_launch("disparity loss backward");
 }
 
 GA_EXPORT int ganet_selftest_dpp_wave(int *scratch_dev, int *host_out, void *stream)

@@ -15,7 +15,7 @@ from .GANet import _check, _p, _sga_infer, _stream
 
 __all__ = ["L1NormalizeGroupsFunction", "NormDisparityRegressionFunction", "normalize_guidance", "normalize_filters",
            "sga_forward_infer", "SoftminFunction", "SoftminDisparityRegressionFunction", "TrilinearUpsampleFunction", "LgaRegressFunction",
-           "ResidualReluFunction"]
+           "ResidualReluFunction", "DisparityLossFunction", "disparity_loss_workspace"]
 
 
 def _lib():
@@ -308,3 +308,68 @@ class ResidualReluFunction(Function):
                 g_t = g_rem
                 _lib().call("ganet_residual_relu_backward", _p(y), _p(g), None, None, _p(g_rem), N, C, D, H, W, _stream())
         return g_t, g_rem, None, None, None
+
+
+def disparity_loss_workspace(like, N, H, W):
+    """the fp64 scratch ganet_disparity_loss_forward wants for [N,H,W] maps, on `like`'s device"""
+    n = _lib().query("ganet_disparity_loss_workspace", N, H, W)
+    return torch.empty(n, dtype=torch.float64, device=like.device)
+
+
+class DisparityLossFunction(Function):
+    """loss, stats = DisparityLossFunction.apply(target, params, workspace, kinds, mask_mode, *predictions)
+
+    The criterion of train.py:100-118 and the error read-out of train.py:126 / evaluation.py:199-202 in two launches (one
+    more for the backward), with no `d[mask]` gather and no host round trip -- so it runs under
+    torch.cuda.set_sync_debug_mode("error") and inside a captured graph.
+      predictions  1..3 maps [N,H,W];  target [N,H,W] (never gets a gradient)
+      params       device tensor of 8 floats {hi, lo, w0, w1, w2, thresh, alpha, rate_thresh}
+      workspace    disparity_loss_workspace(...), private to the call until it has run on the stream
+      kinds        per map 0 (smooth-L1) | 1 (MyLoss2(thresh, alpha), the reference's sequential masked updates)
+      mask_mode    0: target < hi | 1: lo <= target <= hi
+    loss: 0-d, sum_k w_k * mean over the valid pixels of rho_k;  stats: [1 + 3P] = count, then per map mean rho, mean |r|
+    (EPE) and the fraction with |r| > rate_thresh; not differentiable.
+    WITHOUT A VALID PIXEL the loss and all stats are 0 and the backward writes all-zero maps that are still attached to
+    the forward graph -- deliberately not the NaN that stock torch gives for the mean of an empty selection."""
+
+    @staticmethod
+    def forward(ctx, target, params, workspace, kinds, mask_mode, *preds):
+        P = len(preds)
+        if not 1 <= P <= 3 or len(kinds) != P:
+            raise ValueError("1..3 prediction maps with one kind each")
+        _check(target, params, *preds)
+        if target.dim() != 3 or any(p.shape != target.shape for p in preds):
+            raise ValueError(f"expected [N,H,W] maps of one shape, got {[tuple(p.shape) for p in preds]} and {tuple(target.shape)}")
+        if params.numel() != 8:
+            raise ValueError("params: 8 floats {hi, lo, w0, w1, w2, thresh, alpha, rate_thresh}")
+        if not workspace.is_cuda or workspace.device != target.device or workspace.dtype != torch.float64 or not workspace.is_contiguous():
+            raise ValueError("workspace: a contiguous float64 tensor on the maps' device")
+        N, H, W = target.shape
+        if workspace.numel() < _lib().query("ganet_disparity_loss_workspace", N, H, W):
+            raise ValueError("workspace too small: see disparity_loss_workspace")
+        ctx.args = (N, H, W, P) + tuple(list(kinds) + [0] * (3 - P)) + (int(mask_mode),)
+        with torch.cuda.device_of(target):
+            loss = torch.empty((), dtype=target.dtype, device=target.device)
+            stats = torch.empty(1 + 3 * P, dtype=target.dtype, device=target.device)
+            ptrs = [_p(p) for p in preds] + [None] * (3 - P)
+            _lib().call("ganet_disparity_loss_forward", *ptrs, _p(target), _p(params), _p(workspace), _p(loss), _p(stats),
+                        *ctx.args, _stream())
+        ctx.save_for_backward(target, params, stats, *preds)
+        ctx.mark_non_differentiable(stats)
+        return loss, stats
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_stats):
+        target, params, stats, *preds = ctx.saved_tensors
+        P = len(preds)
+        want = ctx.needs_input_grad[5:]
+        grads = [None] * P
+        if any(want):
+            g = grad_loss.to(torch.float32).contiguous()
+            _check(g)
+            with torch.cuda.device_of(target):
+                grads = [torch.empty_like(p) if w else None for p, w in zip(preds, want)]
+                _lib().call("ganet_disparity_loss_backward", *([_p(p) for p in preds] + [None] * (3 - P)), _p(target), _p(params),
+                            _p(stats), _p(g), *([_p(t) if t is not None else None for t in grads] + [None] * (3 - P)),
+                            *ctx.args, _stream())
+        return (None, None, None, None, None) + tuple(grads)

@@ -3,13 +3,13 @@ reference-compatible modules in ganet_amd.modules.GANet are unchanged."""
 import torch
 from torch.nn.modules.module import Module
 
-from ..functions.fused import (LgaRegressFunction, NormDisparityRegressionFunction, ResidualReluFunction,
+from ..functions.fused import (DisparityLossFunction, LgaRegressFunction, NormDisparityRegressionFunction, ResidualReluFunction,
                                SoftminDisparityRegressionFunction, SoftminFunction, TrilinearUpsampleFunction,
-                               normalize_filters, normalize_guidance, sga_forward_infer)
+                               disparity_loss_workspace, normalize_filters, normalize_guidance, sga_forward_infer)
 from ..functions.GANet import Lga2Function, LgaFunction, SgaFunction
 
 __all__ = ["GuidedSGA", "GuidedSGABnRelu", "NormalizedLGA2", "NormDisparityRegression", "SoftminDisparityRegression",
-           "DispAggTail", "TrilinearUpsample", "ResidualBnRelu", "folded_bn"]
+           "DispAggTail", "TrilinearUpsample", "ResidualBnRelu", "DisparityLoss", "folded_bn"]
 
 
 def folded_bn(bn, refresh=False):
@@ -160,3 +160,60 @@ class TrilinearUpsample(Module):
 
     def forward(self, x, size):
         return TrilinearUpsampleFunction.apply(x.contiguous(), tuple(int(v) for v in size))
+
+
+class DisparityLoss(Module):
+    """The training criterion of train.py:100-118 with its error read-out (train.py:126, evaluation.py:199-202) as ONE op:
+    loss, stats = DisparityLoss(...)(outputs, target), outputs = the model's 1..3 disparity maps [N,H,W].
+
+      loss   = sum_k weights[k] * mean over the valid pixels of rho_k(|outputs[k] - target|)
+               kinds[k]: "sl1" (F.smooth_l1_loss) | "myloss2" (MyLoss2(thresh, alpha))
+      stats  = [count, then per map: mean rho, mean |r| (end-point error), fraction with |r| > rate_threshold]
+               (stats[self.epe_index] is the last map's EPE, what train.py:126 reports); not differentiable
+      valid  mask="train": target < max_disp (train.py:100);  "eval": lo <= target <= max_disp (evaluation.py:199)
+
+    No boolean indexing, no host synchronisation: the op can be captured in a graph.  WITHOUT A VALID PIXEL the loss and the
+    stats are 0 (stock torch: NaN) and the backward hands all-zero gradients to every map -- what a rank with an empty
+    shard needs to run the same backward graph as its peers (harness/steps.py).
+    The parameter tensor and the fp64 workspace are kept per device; the workspace is in use from the call until its two
+    launches have run, so one instance serves one stream at a time."""
+
+    KINDS = {"sl1": 0, "myloss2": 1}
+
+    def __init__(self, max_disp, weights, kinds, thresh=3, alpha=2, rate_threshold=3.0, mask="train", lo=0.001):
+        super().__init__()
+        if not 1 <= len(weights) <= 3 or len(kinds) != len(weights):
+            raise ValueError("1..3 weights with one kind each")
+        if mask not in ("train", "eval"):
+            raise ValueError('mask: "train" | "eval"')
+        self.kinds = tuple(self.KINDS[k] for k in kinds)
+        self.mask_mode = 0 if mask == "train" else 1
+        w = [float(v) for v in weights] + [0.0] * (3 - len(weights))
+        self.values = [float(max_disp), float(lo)] + w + [float(thresh), float(alpha), float(rate_threshold)]
+        self.epe_index = 3 * (len(weights) - 1) + 2
+        self._params, self._workspace = {}, {}
+
+    @classmethod
+    def ganet_deep(cls, max_disp=192, kitti=True, **kw):
+        """train.py:106-111: 0.2 * sl1(disp0) + 0.6 * sl1(disp1) + L(disp2), L = MyLoss2(thresh=3, alpha=2) on KITTI, else sl1"""
+        return cls(max_disp, (0.2, 0.6, 1.0), ("sl1", "sl1", "myloss2" if kitti else "sl1"), thresh=3, alpha=2, **kw)
+
+    @classmethod
+    def ganet11(cls, max_disp=192, kitti=True, **kw):
+        """train.py:112-118: 0.4 * sl1(disp1) + 1.2 * L(disp2)"""
+        return cls(max_disp, (0.4, 1.2), ("sl1", "myloss2" if kitti else "sl1"), thresh=3, alpha=2, **kw)
+
+    @classmethod
+    def for_model(cls, name, max_disp=192, kitti=True, **kw):
+        return (cls.ganet11 if name == "GANet11" else cls.ganet_deep)(max_disp, kitti, **kw)
+
+    def forward(self, outputs, target):
+        outputs = [o.contiguous() for o in outputs]
+        target = target.contiguous()
+        dev = target.device
+        if dev not in self._params:
+            self._params[dev] = torch.tensor(self.values, dtype=torch.float32).to(dev)
+        need = (dev, tuple(target.shape))
+        if need not in self._workspace:
+            self._workspace[need] = disparity_loss_workspace(target, *target.shape)
+        return DisparityLossFunction.apply(target, self._params[dev], self._workspace[need], self.kinds, self.mask_mode, *outputs)

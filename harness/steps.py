@@ -57,8 +57,11 @@ def loss_mix(name, outputs, target, mask, crit):
     return 0.2 * l1(disp0) + 0.6 * l1(disp1) + crit(disp2[mask], target[mask])
 
 
-def train_step(model, optimizer, name, left, right, target, max_disp, crit):
-    """One optimisation step (train.py:85-120).  Returns (loss, mean abs error of the last disparity)."""
+def train_step(model, optimizer, name, left, right, target, max_disp, crit, fused_loss=None):
+    """One optimisation step (train.py:85-120).  Returns (loss, mean abs error of the last disparity).
+    fused_loss: a ganet_amd.modules.fused.DisparityLoss built for this model and max_disp; the loss mix and the error then
+    come from its one op (`name` and `crit` are not used), and a rank without a valid pixel needs no branch of its own: with
+    a count of zero the op returns loss 0 and its backward hands all-zero gradients to every output."""
     model.train()
     mask = (target < max_disp).detach()
     # train.py:97-99 skips a batch without valid pixels.  With one process per GPU the skip has to be COLLECTIVE: a rank that
@@ -74,7 +77,10 @@ def train_step(model, optimizer, name, left, right, target, max_disp, crit):
         return None, None
     optimizer.zero_grad()
     outputs = model(left, right)
-    if int(nvalid) == 0:
+    if fused_loss is not None:
+        loss, stats = fused_loss(outputs, target)
+        err = stats[fused_loss.epe_index].detach()
+    elif int(nvalid) == 0:
         # EVERY rank runs the same backward graph: DDP's reducer marks unused parameters ready on its own (a loss that
         # touched them directly made it mark them twice), and SyncBatchNorm's backward all-reduces on the default group -- a rank
         # that bypassed the data path would issue a different collective sequence than its peers.  So the zero-weighted loss

@@ -72,19 +72,23 @@ def run(args, hook=None):
     if args.resume:
         epoch0, _ = steps.load_checkpoint(args.resume, model, None)
     crit = steps.criterion(bool(args.kitti))
+    fused_loss = None
+    if args.fused:
+        from ganet_amd.modules.fused import DisparityLoss
+        fused_loss = DisparityLoss.for_model(args.model, args.max_disp, bool(args.kitti))
     # every rank its own samples: the batch dimension is what shards (no data-path collective inside the ops)
     left, right, target = steps.synthetic_batch(args.batch, args.crop_height, args.crop_width, args.max_disp, dev,
                                                 seed=123 + ctx.rank)
     sync = (lambda: None) if cpu else torch.cuda.synchronize
     losses = []
     for _ in range(args.warmup):
-        steps.train_step(model, opt, args.model, left, right, target, args.max_disp, crit)
+        steps.train_step(model, opt, args.model, left, right, target, args.max_disp, crit, fused_loss)
     if not cpu:
         torch.cuda.reset_peak_memory_stats()
 
     def timed():
         for _ in range(args.steps):
-            loss, err = steps.train_step(model, opt, args.model, left, right, target, args.max_disp, crit)
+            loss, err = steps.train_step(model, opt, args.model, left, right, target, args.max_disp, crit, fused_loss)
             if loss is not None:      # (a step every rank skipped: no valid pixel anywhere)
                 losses.append(float(loss))
 
@@ -92,7 +96,7 @@ def run(args, hook=None):
     share = None
     if args.kernel_share and ctx.rank == 0 and not cpu and ctx.world_size == 1:
         from harness.kernel_share import profile_passes
-        share = profile_passes(lambda: steps.train_step(model, opt, args.model, left, right, target, args.max_disp, crit), 2)
+        share = profile_passes(lambda: steps.train_step(model, opt, args.model, left, right, target, args.max_disp, crit, fused_loss), 2)
     if args.save and ctx.rank == 0:
         steps.save_checkpoint(args.save, model, opt, epoch0 + 1)
     line = {"what": "training step, reference model on the drop-in ops", "model": args.model, "n_gpus": ctx.world_size,

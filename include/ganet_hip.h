@@ -35,7 +35,7 @@ extern "C" {
 #define GANET_E_UNSUPPORTED (-2)  /* shape outside the compiled kernel set         */
 #define GANET_E_RUNTIME (-3)      /* HIP runtime / launch error                    */
 
-#define GANET_ABI_VERSION 11      /* v11 = v10 + ganet_residual_relu_forward / _backward (SGABlock's residual epilogue) */
+#define GANET_ABI_VERSION 12      /* v12 = v11 + ganet_disparity_loss_workspace / _forward / _backward (the training criterion) */
 int ganet_abi_version(void);
 const char *ganet_last_error(void);
 /* 1 if this build runs the lockstep CPU emulator (tests only), 0 for the gfx950 build */
@@ -281,6 +281,34 @@ int ganet_residual_relu_forward(const float *t, const float *rem, const float *b
                                 float *y, int N, int C, int D, int H, int W, void *stream);
 int ganet_residual_relu_backward(const float *y, const float *grad_y, const float *bn_scale, float *grad_t,
                                  float *grad_rem, int N, int C, int D, int H, int W, void *stream);
+
+/* ---------------------------------------------------------------- criterion ------ */
+
+/* ABI v12.  The training criterion and the error read-out over up to three disparity maps p_k [N,H,W] (unused ones NULL)
+ * against one target [N,H,W], in two launches forward and one backward, without a host round trip and without atomics
+ * (bit-reproducible).  params: DEVICE array of 8 floats {hi, lo, w0, w1, w2, thresh, alpha, rate_thresh}.
+ *   valid pixel  mask_mode 0: target < hi (train.py:100);  1: lo <= target && target <= hi (evaluation.py:199).  NaN: invalid.
+ *   r = p - t    kind 0: smooth-L1 (beta = 1);  kind 1: MyLoss2(thresh, alpha) as the reference applies it -- three masked
+ *                updates of one buffer in sequence, for the value and, separately, for its slope table
+ *                (libs/GANet/functions/GANet.py:264-289).  Every fp32 operation is rounded on its own.
+ *   loss [1]     = sum_k w_k * mean_valid rho_k(|r_k|)
+ *   stats [1+3P] = count, then per map: mean rho, mean |r| (end-point error), fraction with |r| > rate_thresh
+ *   g_k          = valid ? sign(r_k) * slope_k(|r_k|) * (float)(w_k * grad_loss / count) : +0;  grad_loss: DEVICE scalar,
+ *                count: stats[0] of the forward.  A NULL g_k: that map is not wanted.
+ * count == 0 gives loss 0, stats 0 and all-zero gradient maps -- deliberately not the NaN that the mean over an empty
+ * selection is in stock PyTorch.  Invalid pixels are left out by a select: a NaN / inf prediction there harms nothing.
+ * workspace: ganet_disparity_loss_workspace(N, H, W) doubles (the size for P = 3), private to the call until it has run.
+ * N * H * W >= 2^24: GANET_E_UNSUPPORTED (counts are reported as floats).  Bad P / kind / mask_mode: GANET_E_INVALID.
+ * Replaces: train.py:100-118 (mask, `d[mask]` gathers, F.smooth_l1_loss / MyLoss2 terms and their weighted sum) with its
+ *           autograd backward and MyLoss2Function.backward, train.py:126 and evaluation.py:199-202 (error, rate). */
+int ganet_disparity_loss_workspace(int N, int H, int W);
+int ganet_disparity_loss_forward(const float *p0, const float *p1, const float *p2, const float *target,
+                                 const float *params, double *workspace, float *loss, float *stats,
+                                 int N, int H, int W, int P, int kind0, int kind1, int kind2, int mask_mode, void *stream);
+int ganet_disparity_loss_backward(const float *p0, const float *p1, const float *p2, const float *target,
+                                  const float *params, const float *stats, const float *grad_loss,
+                                  float *g0, float *g1, float *g2,
+                                  int N, int H, int W, int P, int kind0, int kind1, int kind2, int mask_mode, void *stream);
 
 /* ---------------------------------------------------------------- diagnostics ---- */
 
