@@ -48,6 +48,9 @@ GA_DEV f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
 GA_DEV f2 add2(f2 a, f2 b) { return a + b; }
 #endif
 GA_DEV f2 mk2(float a, float b) { f2 r; r.x = a; r.y = b; return r; }
+// ReLU as ATen's relu / threshold_backward have it: a NaN passes through (fmaxf(v, 0.f) would return 0 for it).  Used by every
+// fused ReLU epilogue: the residual tail (misc_kernels.h) and the BatchNorm + ReLU of the SGA inference merge.
+GA_DEV float relu_keep_nan(float v) { return v <= 0.f ? 0.f : v; }
 // optimisation fence on a packed value: it has to be complete HERE (no sinking into a later branch)
 #if defined(GA_HIPSIM)
 #define GA_KEEP_F2(v) ((void)0)

@@ -589,7 +589,6 @@ softmin_regression_bwd(const float *__restrict__ x, const float *__restrict__ ou
 //                                                  on t = bn(conv) as PyTorch computed it (training mode).
 // Stock PyTorch: batch_norm (r V, w V) + add_ (r 2V, w V) + relu_ (r V, w V) = 7 V; here 2 V in, 1 V out.  y may BE t (the
 // reference adds in place as well), which is why neither carries __restrict__.  blockIdx.y = slice (n, c): no division per element.
-GA_DEV float relu_keep_nan(float v) { return v <= 0.f ? 0.f : v; }      // ATen's relu / threshold_backward: a NaN passes through
 template <bool VEC4>
 __global__ void __launch_bounds__(256)
 residual_relu_fwd(const float *t, const float *__restrict__ rem, const float *__restrict__ scale,

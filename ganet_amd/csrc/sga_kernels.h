@@ -795,7 +795,7 @@ sga_merge_infer(const float *__restrict__ A0, const float *__restrict__ A1, cons
         if (v[j] < w1[j]) v[j] = w1[j];
         if (v[j] < w2[j]) v[j] = w2[j];
         if (v[j] < w3[j]) v[j] = w3[j];
-        if (scale) v[j] = fmaxf(fmaf(v[j], sc, sh), 0.f);
+        if (scale) v[j] = relu_keep_nan(fmaf(v[j], sc, sh));
       }
       f4 r; r.x = v[0]; r.y = v[1]; r.z = v[2]; r.w = v[3];
       *reinterpret_cast<f4 *>(out + e) = r;
@@ -807,7 +807,7 @@ sga_merge_infer(const float *__restrict__ A0, const float *__restrict__ A1, cons
       if (v < b) v = b;
       if (v < c_) v = c_;
       if (v < d) v = d;
-      if (scale) { const int ch = (int)((e / slice) % C); v = fmaxf(fmaf(v, scale[ch], shift[ch]), 0.f); }
+      if (scale) { const int ch = (int)((e / slice) % C); v = relu_keep_nan(fmaf(v, scale[ch], shift[ch])); }
       out[e] = v;
     }
   }

@@ -205,8 +205,8 @@ sga_row_fwd(const float *__restrict__ x, const float *__restrict__ g, float *__r
             v.x = v.x < o.x ? o.x : v.x; v.y = v.y < o.y ? o.y : v.y;
             v.z = v.z < o.z ? o.z : v.z; v.w = v.w < o.w ? o.w : v.w;
             if (geo.out_mode == 2) {
-              v.x = fmaxf(fmaf(v.x, bn_sc[q], bn_sh[q]), 0.f); v.y = fmaxf(fmaf(v.y, bn_sc[q], bn_sh[q]), 0.f);
-              v.z = fmaxf(fmaf(v.z, bn_sc[q], bn_sh[q]), 0.f); v.w = fmaxf(fmaf(v.w, bn_sc[q], bn_sh[q]), 0.f);
+              v.x = relu_keep_nan(fmaf(v.x, bn_sc[q], bn_sh[q])); v.y = relu_keep_nan(fmaf(v.y, bn_sc[q], bn_sh[q]));
+              v.z = relu_keep_nan(fmaf(v.z, bn_sc[q], bn_sh[q])); v.w = relu_keep_nan(fmaf(v.w, bn_sc[q], bn_sh[q]));
             }
             *reinterpret_cast<f4 *>(Ab + (i64)pl * geo.HW + wq) = v;      // (read back by the next direction's scan: a plain store)
           } else {

@@ -121,6 +121,51 @@ def lga_inputs_exact(shape, r, seed):
     return x, f, gy
 
 
+# ---- non-finite inputs for the fused BatchNorm + ReLU epilogue of ganet_sga_forward_infer ------------------------------------------
+NONFINITE_SHAPES = [(2, 3, 9, 4, 8), (2, 3, 8, 3, 5), (2, 3, 5, 3, 5)]     # row kernel's epilogue | merge, 16-byte form | merge, scalar
+NONFINITE_SCALE = np.array([-2.0, 0.5, -0.5], np.float32)                  # powers of two: scale * v is exact, so fmaf(v, sc, sh)
+NONFINITE_SHIFT = np.array([0.75, -1.25, 0.5], np.float32)                 # and fp32 multiply-then-add round once, alike
+
+
+def sga_inputs_nonfinite(shape, seed):
+    """x = randn with ONE special element per (n, c) slice -- NaN, +Inf or -Inf, kind (n + c) % 3 -- and strictly positive
+    normalised guidance taps, so that an infinity spreads as that infinity (no 0 * Inf, no Inf - Inf inside a slice).  With
+    NONFINITE_SCALE every kind meets a scale of either sign in some slice: -Inf under a negative scale becomes +Inf.
+    -> (x, gs, raw guidance [N, 20 C, H, W] that L1-normalises to gs' ratios, for the module form)"""
+    rng = np.random.default_rng(seed)
+    N, C, D, H, W = shape
+    assert C == 3 and N >= 2
+    x = rng.standard_normal(shape).astype(np.float32)
+    for n in range(N):
+        for c in range(C):
+            x[n, c, D // 2, H // 2, W // 2] = (np.nan, np.inf, -np.inf)[(n + c) % 3]
+    raw = (np.abs(rng.standard_normal((N, 4, C, 5, H, W))) + 0.05).astype(np.float32)
+    gs = [l1norm(raw[:, k], 2) for k in range(4)]
+    return x, gs, np.ascontiguousarray(raw.reshape(N, 20 * C, H, W))
+
+
+def bn_relu_keep_nan(v, scale, shift):
+    """relu(scale[c] * v + shift[c]) on [N,C,D,H,W] in fp32 with the ReLU of ATen: a NaN passes through"""
+    C = v.shape[1]
+    with np.errstate(invalid="ignore"):
+        pre = v.astype(np.float32) * scale.astype(np.float32).reshape(1, C, 1, 1, 1) + shift.astype(np.float32).reshape(1, C, 1, 1, 1)
+        return np.where(pre <= 0, np.float32(0), pre).astype(np.float32)
+
+
+def assert_same_with_nan(got, want, what=""):
+    """the NaN positions and every other value (infinities included) are equal"""
+    assert np.array_equal(np.isnan(got), np.isnan(want)), (what, "NaN positions", int(np.isnan(got).sum()), int(np.isnan(want).sum()))
+    ok = ~np.isnan(want)
+    assert np.array_equal(got[ok], want[ok]), (what, int((got[ok] != want[ok]).sum()), "values differ")
+
+
+def assert_nonfinite_reach_the_epilogue(plain, want):
+    """the plain maximum holds each kind, and the epilogue's yardstick turns a -Inf into +Inf somewhere (negative scale)"""
+    assert np.isnan(plain).any() and np.isposinf(plain).any() and np.isneginf(plain).any()
+    assert (np.isneginf(plain) & np.isposinf(want)).any() and (np.isposinf(plain) & (want == 0)).any()
+    assert (np.isneginf(plain) & (want == 0)).any() and (np.isposinf(plain) & np.isposinf(want)).any()
+
+
 def oracle_sga_want(oracle, x, gs, go):
     """everything check_sga_forward_backward / check_sga_compat compare with, from the oracle (A0..A3 included)"""
     out, tmp, mask = oracle.sga_forward(x, *gs)

@@ -221,6 +221,38 @@ def test_guided_sga_bn_relu_eval_matches_op_chain(torch_mod, port_oracle):
     assert np.abs(_np(y) - want.numpy()).max() <= pc.TOL
 
 
+@pytest.mark.parametrize("shape", pc.NONFINITE_SHAPES, ids=["row-epilogue", "merge-vec4", "merge-scalar"])
+def test_guided_sga_bn_relu_eval_keeps_nan_and_inf(torch_mod, shape):
+    """The device twin of tests/test_sim_fused.py::test_sga_forward_infer_bn_relu_epilogue_keeps_nan_and_inf, through
+    GuidedSGABnRelu in eval mode: with NaN / +Inf / -Inf in x the fused BatchNorm + ReLU epilogue equals (NaN positions and
+    every other value) both the library's plain maximum pushed through a NaN-passing relu(scale[c] * v + shift[c]) in numpy
+    and the op chain torch.relu(bn(SgaFunction.apply(...))) it replaces.  The BatchNorm is chosen so that both are exact:
+    mean 0, variance + eps = 1 exactly, weights that are powers of two -- one rounding, in the final add, on every side."""
+    torch = torch_mod
+    from ganet_amd.functions.GANet import SgaFunction
+    from ganet_amd.functions.fused import normalize_guidance, sga_forward_infer
+    from ganet_amd.modules.fused import GuidedSGABnRelu, folded_bn
+    x, _, raw = pc.sga_inputs_nonfinite(shape, seed=sum(shape))
+    C = shape[1]
+    bn = torch.nn.BatchNorm3d(C, eps=2.0 ** -10).cuda()
+    with torch.no_grad():
+        bn.weight.copy_(torch.from_numpy(pc.NONFINITE_SCALE)); bn.bias.copy_(torch.from_numpy(pc.NONFINITE_SHIFT))
+        bn.running_mean.zero_(); bn.running_var.fill_(1.0 - 2.0 ** -10)              # var + eps == 1.0 exactly
+    m = GuidedSGABnRelu(bn).eval()
+    dx, dg = torch.from_numpy(x).cuda(), torch.from_numpy(raw).cuda()
+    with torch.no_grad():
+        got = m(dx, dg)
+        ks = normalize_guidance(dg, C)
+        plain = sga_forward_infer(dx, *ks)
+        chain = torch.relu(bn(SgaFunction.apply(dx, *ks)))
+    scale, shift = (_np(t) for t in folded_bn(bn))
+    assert np.array_equal(scale, pc.NONFINITE_SCALE) and np.array_equal(shift, pc.NONFINITE_SHIFT)
+    want = pc.bn_relu_keep_nan(_np(plain), scale, shift)
+    pc.assert_nonfinite_reach_the_epilogue(_np(plain), want)
+    pc.assert_same_with_nan(_np(got), want, "numpy statement")
+    pc.assert_same_with_nan(_np(got), _np(chain), "op chain")
+
+
 def test_softmin_disparity_regression_full_size(torch_mod):
     """SoftminDisparityRegression on [1,193,240,624] == Softmin(dim=1) + DisparityRegression (models/GANet_deep.py:217-219)
     computed with torch's own ops on the GPU, forward and backward."""

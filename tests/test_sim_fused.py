@@ -175,6 +175,32 @@ def test_sga_forward_infer_bn_relu_epilogue(sim, port_oracle, shape, with_bn):
         assert np.array_equal(out, want)
 
 
+@pytest.mark.parametrize("shape", pc.NONFINITE_SHAPES, ids=["row-epilogue", "merge-vec4", "merge-scalar"])
+def test_sga_forward_infer_bn_relu_epilogue_keeps_nan_and_inf(sim, shape):
+    """NaN, +Inf and -Inf in x: the fused epilogue must hand on what relu(bn(.)) of the op chain hands on -- ATen's relu
+    passes a NaN, fmaxf(v, 0) would launder it into 0.  Yardstick: the library's own plain maximum (bn = NULL, same dispatch)
+    pushed through relu(scale[c] * v + shift[c]) in numpy; NaN positions and every other value equal.  The three shapes reach
+    the three places the epilogue is written: the row kernel's copy-out (W % 4 == 0), sga_merge_infer's 16-byte form
+    (W % 4 != 0, slice % 4 == 0) and its scalar form."""
+    x, gs, _ = pc.sga_inputs_nonfinite(shape, seed=sum(shape))
+    N, C, D, H, W = shape
+    fused = sim.query("ganet_sga_forward_infer_scratch", *[pc.guarded_empty(a.shape).ctypes.data for a in [x] + gs + [x]],
+                      N, C, D, H, W) == 0
+    site = "row-epilogue" if fused else ("merge-vec4" if (D * H * W) % 4 == 0 else "merge-scalar")
+    assert site == ["row-epilogue", "merge-vec4", "merge-scalar"][pc.NONFINITE_SHAPES.index(shape)]
+    outs = []
+    for bn in (False, True):
+        A = np.empty((4,) + shape, np.float32)
+        out = np.full(shape, 7.0, np.float32)
+        _call(sim, "ganet_sga_forward_infer", _p(x), *[_p(g) for g in gs], _p(A), _p(out),
+              _p(pc.NONFINITE_SCALE) if bn else None, _p(pc.NONFINITE_SHIFT) if bn else None, N, C, D, H, W, None)
+        outs.append(out)
+    plain, got = outs
+    want = pc.bn_relu_keep_nan(plain, pc.NONFINITE_SCALE, pc.NONFINITE_SHIFT)
+    pc.assert_nonfinite_reach_the_epilogue(plain, want)
+    pc.assert_same_with_nan(got, want)
+
+
 @pytest.mark.parametrize("N,D,H,W", [(1, 7, 3, 5), (2, 193, 2, 3), (1, 16, 4, 4), (2, 193, 2, 4), (1, 5, 3, 8)])
 def test_softmin_forward_backward(sim, N, D, H, W):
     """nn.Softmin(dim=1) (models/GANet_deep.py:244) vs torch on the CPU, incl. large-magnitude inputs."""
