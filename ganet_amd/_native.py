@@ -11,7 +11,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libganet_hip.so"
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -61,6 +61,10 @@ _PROTOS = {
     "ganet_disparity_loss_workspace": [_I] * 3,
     "ganet_disparity_loss_forward": [_P] * 8 + [_I] * 8 + [_P],
     "ganet_disparity_loss_backward": [_P] * 10 + [_I] * 8 + [_P],
+    "ganet_bn_workspace": [_I] * 3,
+    "ganet_bn_train_forward": [_P] * 10 + [_I] * 6 + [_P],
+    "ganet_bn_train_backward": [_P] * 12 + [_I] * 4 + [_P],
+    "ganet_bn_apply_forward": [_P] * 5 + [_I] * 4 + [_P],
     "ganet_selftest_dpp": [_P, _P, _P],
     "ganet_selftest_dpp_wave": [_P, _P, _P],
 }

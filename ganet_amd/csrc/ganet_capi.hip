@@ -2,6 +2,7 @@
 // include/ganet_hip.h, argument validation, kernel selection and launch.
 // Compiled by hipcc for gfx950 (product) and by g++ -DGA_HIPSIM (CPU test emulator).
 #include "ga_common.h"
+#include "bn_kernels.h"
 #include "lga_kernels.h"
 #include "loss_kernels.h"
 #include "misc_kernels.h"
@@ -1527,6 +1528,115 @@ GA_EXPORT int ganet_disparity_loss_backward(const float *p0, const float *p1, co
   if (vec) GA_LAUNCH((loss_bwd<4>), dim3(ew_grid(total / 4)), dim3(256), st, m, target, params, stats, grad_loss, total, P, mask_mode);
   else GA_LAUNCH((loss_bwd<1>), dim3(ew_grid(total)), dim3(256), st, m, target, params, stats, grad_loss, total, P, mask_mode);
   return check_launch("disparity loss backward");
+}
+
+// ---- training-mode BatchNorm + (residual) + ReLU (models/GANet_deep.py:35-41, :270-277) ---------------------------------------
+namespace {
+int bn_rows_cap(int C)
+{
+  const int want = BN_TARGET_BLOCKS / C;
+  return want < 1 ? 1 : (want < BN_MAX_ROWS ? want : BN_MAX_ROWS);
+}
+
+// rows per channel: Rs blocks along a slice (each lane at least one trip), the rest of the cap over the channel's N slices
+int bn_geom(const char *who, int N, int C, int S, bool vec, bool training, BnGeom *g)
+{
+  if (N <= 0 || C <= 0 || S <= 0) return fail(GANET_E_INVALID, "%s: non-positive size N=%d C=%d S=%d", who, N, C, S);
+  if (training && (i64)N * S == 1)
+    return fail(GANET_E_INVALID, "%s: one value per channel (N * S = 1): batch statistics need more", who);
+  if (C > 65535) return fail(GANET_E_UNSUPPORTED, "%s: C=%d > 65535 (grid.y)", who, C);
+  const int cap = bn_rows_cap(C);
+  const i64 want = ((vec ? S / 4 : S) + BN_BLOCK - 1) / BN_BLOCK;
+  g->N = N; g->C = C; g->S = S;
+  g->Rs = (int)(want < cap ? want : cap);
+  g->Rn = cap / g->Rs < N ? cap / g->Rs : N;
+  return GANET_OK;
+}
+float bn_float(int bits)
+{
+  float f;
+  memcpy(&f, &bits, sizeof f);
+  return f;
+}
+}  // namespace
+
+GA_EXPORT int ganet_bn_workspace(int N, int C, int S)
+{
+  BnGeom g;
+  GA_TRY(bn_geom("ganet_bn_workspace", N, C, S, false, true, &g));
+  return 2 * C * bn_rows_cap(C);
+}
+
+GA_EXPORT int ganet_bn_train_forward(const float *x, const float *rem, const float *weight, const float *bias,
+                                     float *running_mean, float *running_var, double *workspace, float *y, float *save_mean,
+                                     float *save_invstd, int N, int C, int S, int momentum_bits, int eps_bits, int relu,
+                                     void *stream)
+{
+  const char *who = "ganet_bn_train_forward";
+  if (!x || !workspace || !y || !save_mean || !save_invstd) return fail(GANET_E_INVALID, "%s: null pointer", who);
+  if ((running_mean == nullptr) != (running_var == nullptr))
+    return fail(GANET_E_INVALID, "%s: running_mean and running_var come together", who);
+  if (y == x || y == rem) return fail(GANET_E_INVALID, "%s: y must not alias an input", who);
+  const bool vec = S % 4 == 0 && aligned16(x) && aligned16(y) && aligned16(rem);
+  BnGeom g;
+  GA_TRY(bn_geom(who, N, C, S, vec, true, &g));
+  const float momentum = bn_float(momentum_bits), eps = bn_float(eps_bits);
+  const dim3 grid(g.Rs * g.Rn, C);
+  hipStream_t st = (hipStream_t)stream;
+  if (vec) GA_LAUNCH((bn_stat_partials<4>), grid, dim3(BN_BLOCK), st, x, workspace, g);
+  else GA_LAUNCH((bn_stat_partials<1>), grid, dim3(BN_BLOCK), st, x, workspace, g);
+  GA_TRY(check_launch("batch norm statistics"));
+  if (vec)
+    GA_LAUNCH((bn_train_apply<4>), grid, dim3(BN_BLOCK), st, x, rem, weight, bias, running_mean, running_var, workspace, y,
+              save_mean, save_invstd, g, momentum, eps, relu);
+  else
+    GA_LAUNCH((bn_train_apply<1>), grid, dim3(BN_BLOCK), st, x, rem, weight, bias, running_mean, running_var, workspace, y,
+              save_mean, save_invstd, g, momentum, eps, relu);
+  return check_launch("batch norm forward");
+}
+
+GA_EXPORT int ganet_bn_train_backward(const float *x, const float *rem, const float *grad_y, const float *weight,
+                                      const float *bias, const float *save_mean, const float *save_invstd, double *workspace,
+                                      float *grad_x, float *grad_rem, float *grad_weight, float *grad_bias, int N, int C, int S,
+                                      int relu, void *stream)
+{
+  const char *who = "ganet_bn_train_backward";
+  if (!x || !grad_y || !save_mean || !save_invstd || !workspace) return fail(GANET_E_INVALID, "%s: null pointer", who);
+  for (const float *o : {(const float *)grad_x, (const float *)grad_rem})
+    if (o && (o == x || o == rem || o == grad_y)) return fail(GANET_E_INVALID, "%s: a gradient must not alias an input", who);
+  if (grad_x && grad_x == grad_rem) return fail(GANET_E_INVALID, "%s: grad_x and grad_rem are two buffers", who);
+  const bool vec = S % 4 == 0 && aligned16(x) && aligned16(rem) && aligned16(grad_y) && aligned16(grad_x) && aligned16(grad_rem);
+  BnGeom g;
+  GA_TRY(bn_geom(who, N, C, S, vec, true, &g));
+  if (!grad_x && !grad_rem && !grad_weight && !grad_bias) return GANET_OK;
+  const dim3 grid(g.Rs * g.Rn, C), apply_grid = (grad_x || grad_rem) ? grid : dim3(1, C);
+  hipStream_t st = (hipStream_t)stream;
+  if (vec) GA_LAUNCH((bn_bwd_partials<4>), grid, dim3(BN_BLOCK), st, x, rem, grad_y, weight, bias, save_mean, save_invstd, workspace, g, relu);
+  else GA_LAUNCH((bn_bwd_partials<1>), grid, dim3(BN_BLOCK), st, x, rem, grad_y, weight, bias, save_mean, save_invstd, workspace, g, relu);
+  GA_TRY(check_launch("batch norm backward sums"));
+  if (vec)
+    GA_LAUNCH((bn_bwd_apply<4>), apply_grid, dim3(BN_BLOCK), st, x, rem, grad_y, weight, bias, save_mean, save_invstd, workspace,
+              grad_x, grad_rem, grad_weight, grad_bias, g, relu);
+  else
+    GA_LAUNCH((bn_bwd_apply<1>), apply_grid, dim3(BN_BLOCK), st, x, rem, grad_y, weight, bias, save_mean, save_invstd, workspace,
+              grad_x, grad_rem, grad_weight, grad_bias, g, relu);
+  return check_launch("batch norm backward");
+}
+
+GA_EXPORT int ganet_bn_apply_forward(const float *x, const float *rem, const float *scale, const float *shift, float *y, int N,
+                                     int C, int S, int relu, void *stream)
+{
+  const char *who = "ganet_bn_apply_forward";
+  if (!x || !scale || !shift || !y) return fail(GANET_E_INVALID, "%s: null pointer", who);
+  if (y == rem) return fail(GANET_E_INVALID, "%s: y may alias x, not rem", who);
+  const bool vec = S % 4 == 0 && aligned16(x) && aligned16(y) && aligned16(rem);
+  BnGeom g;
+  GA_TRY(bn_geom(who, N, C, S, vec, false, &g));
+  const dim3 grid(g.Rs * g.Rn, C);
+  hipStream_t st = (hipStream_t)stream;
+  if (vec) GA_LAUNCH((bn_affine_apply<4>), grid, dim3(BN_BLOCK), st, x, rem, scale, shift, y, g, relu);
+  else GA_LAUNCH((bn_affine_apply<1>), grid, dim3(BN_BLOCK), st, x, rem, scale, shift, y, g, relu);
+  return check_launch("batch norm apply");
 }
 
 GA_EXPORT int ganet_selftest_dpp_wave(int *scratch_dev, int *host_out, void *stream)

@@ -7,15 +7,18 @@ In the reference these are chains of stock PyTorch ops AROUND the guided-aggrega
 They sit BESIDE the drop-in API (libs/GANet/... keeps the reference's call forms unchanged): a model opts in by
 calling GuidedSGA / NormalizedLGA2 / DispAggTail from ganet_amd.modules.fused instead of the op chains.
 """
+import struct
+
 import torch
 from torch.autograd import Function
+from torch.autograd.function import once_differentiable
 
 from .. import _native
 from .GANet import _check, _p, _sga_infer, _stream
 
 __all__ = ["L1NormalizeGroupsFunction", "NormDisparityRegressionFunction", "normalize_guidance", "normalize_filters",
            "sga_forward_infer", "SoftminFunction", "SoftminDisparityRegressionFunction", "TrilinearUpsampleFunction", "LgaRegressFunction",
-           "ResidualReluFunction", "DisparityLossFunction", "disparity_loss_workspace"]
+           "ResidualReluFunction", "DisparityLossFunction", "disparity_loss_workspace", "BnReluFunction", "BnApplyFunction"]
 
 
 def _lib():
@@ -373,3 +376,110 @@ class DisparityLossFunction(Function):
                             _p(stats), _p(g), *([_p(t) if t is not None else None for t in grads] + [None] * (3 - P)),
                             *ctx.args, _stream())
         return (None, None, None, None, None) + tuple(grads)
+
+
+def _float_bits(v):
+    """an fp32 value as the int that carries it across the C ABI"""
+    return struct.unpack("<i", struct.pack("<f", float(v)))[0]
+
+
+def _opt(t):
+    return _p(t) if t is not None else None
+
+
+class BnReluFunction(Function):
+    """y = BnReluFunction.apply(x, rem, weight, bias, running_mean, running_var, momentum, eps, relu)
+
+    `conv -> bn -> F.relu(inplace=True)` behind every BasicConv (models/GANet_deep.py:35-41) and the BatchNorm3d + `x += rem`
+    + relu of SGABlock's tail (:270-277) with BATCH statistics, in two launches each way (ganet_bn_train_forward / _backward):
+      y = relu(weight (x - mean) invstd + bias [+ rem])     x [N,C,*] contiguous fp32; rem, weight, bias, running_*: None or given
+    running_mean / running_var are updated in place as F.batch_norm(training=True) does (momentum: a float).  Saved for the
+    backward: x, rem (when given), weight, bias and the two [C] statistics -- never y: the backward recomputes the ReLU mask
+    from x.  Only the gradients autograd asks for are computed.  Not twice differentiable.  The fp64 scratch of both passes is
+    a fresh 2 * rows * C doubles from the caching allocator: no state, any stream, capturable."""
+
+    @staticmethod
+    def forward(ctx, x, rem, weight, bias, running_mean, running_var, momentum, eps, relu):
+        _check(*[t for t in (x, rem, weight, bias, running_mean, running_var) if t is not None])
+        if x.dim() < 3:
+            raise ValueError(f"expected [N,C,*], got {tuple(x.shape)}")
+        if rem is not None and rem.shape != x.shape:
+            raise ValueError(f"x and rem must have one shape, got {tuple(x.shape)} and {tuple(rem.shape)}")
+        N, C = x.shape[:2]
+        S = x.numel() // (N * C)
+        if any(t is not None and t.numel() != C for t in (weight, bias, running_mean, running_var)):
+            raise ValueError("weight / bias / running statistics must have one entry per channel")
+        if (weight is None) != (bias is None) or (running_mean is None) != (running_var is None):
+            raise ValueError("weight and bias, running_mean and running_var come together")
+        ctx.args = (N, C, S, int(bool(relu)))
+        with torch.cuda.device_of(x):
+            ws = torch.empty(_lib().query("ganet_bn_workspace", N, C, S), dtype=torch.float64, device=x.device)
+            y = torch.empty_like(x)
+            mean = torch.empty(C, dtype=x.dtype, device=x.device)
+            invstd = torch.empty_like(mean)
+            _lib().call("ganet_bn_train_forward", _p(x), _opt(rem), _opt(weight), _opt(bias), _opt(running_mean), _opt(running_var),
+                        _p(ws), _p(y), _p(mean), _p(invstd), N, C, S, _float_bits(momentum), _float_bits(eps), ctx.args[3], _stream())
+        ctx.save_for_backward(x, rem, weight, bias, mean, invstd)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_y):
+        x, rem, weight, bias, mean, invstd = ctx.saved_tensors
+        N, C, S, relu = ctx.args
+        need = ctx.needs_input_grad
+        g = grad_y.contiguous()
+        _check(g)
+        with torch.cuda.device_of(x):
+            gx = torch.empty_like(x) if need[0] else None
+            # without the ReLU, g IS grad_y: the residual takes the incoming gradient itself
+            g_rem = (torch.empty_like(x) if relu else g) if rem is not None and need[1] else None
+            gw = torch.empty_like(mean) if weight is not None and need[2] else None
+            gb = torch.empty_like(mean) if bias is not None and need[3] else None
+            if gx is not None or gw is not None or gb is not None or (g_rem is not None and relu):
+                ws = torch.empty(_lib().query("ganet_bn_workspace", N, C, S), dtype=torch.float64, device=x.device)
+                _lib().call("ganet_bn_train_backward", _p(x), _opt(rem), _p(g), _opt(weight), _opt(bias), _p(mean), _p(invstd), _p(ws),
+                            _opt(gx), _opt(g_rem) if relu else None, _opt(gw), _opt(gb), N, C, S, relu, _stream())
+        return gx, g_rem, gw, gb, None, None, None, None, None
+
+
+class BnApplyFunction(Function):
+    """y = relu(scale[c] * x + shift[c] [+ rem]): a BatchNorm folded from its running statistics (eval mode; scale and shift
+    are constants here), the residual and the ReLU in ONE pass (ganet_bn_apply_forward) -- `inplace` writes y over x.
+    Backward: g = grad_y where y > 0; rem takes g, x takes scale[c] * g (ganet_residual_relu_backward on the saved y)."""
+
+    @staticmethod
+    def forward(ctx, x, rem, scale, shift, relu, inplace):
+        _check(*[t for t in (x, rem, scale, shift) if t is not None])
+        if x.dim() < 3 or (rem is not None and rem.shape != x.shape):
+            raise ValueError("expected [N,C,*] volumes of one shape")
+        N, C = x.shape[:2]
+        S = x.numel() // (N * C)
+        if scale.numel() != C or shift.numel() != C:
+            raise ValueError("scale / shift must have one entry per channel")
+        ctx.args = (N, C, S, int(bool(relu)))
+        with torch.cuda.device_of(x):
+            y = x if inplace else torch.empty_like(x)
+            _lib().call("ganet_bn_apply_forward", _p(x), _opt(rem), _p(scale), _p(shift), _p(y), N, C, S, ctx.args[3], _stream())
+        if inplace:
+            ctx.mark_dirty(x)
+        ctx.has_rem = rem is not None
+        ctx.save_for_backward(scale, *([y] if relu else []))
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_y):
+        scale = ctx.saved_tensors[0]
+        N, C, S, relu = ctx.args
+        g = grad_y.contiguous()
+        _check(g)
+        with torch.cuda.device_of(g):
+            if relu:
+                y = ctx.saved_tensors[1]
+                g_rem, gx = torch.empty_like(g), torch.empty_like(g)
+                _lib().call("ganet_residual_relu_backward", _p(y), _p(g), _p(scale), _p(gx), _p(g_rem), N, C, 1, 1, S, _stream())
+            else:
+                g_rem, gx = g, g * scale.view((1, C) + (1,) * (g.dim() - 2))
+        return (gx if ctx.needs_input_grad[0] else None, g_rem if ctx.has_rem and ctx.needs_input_grad[1] else None,
+                None, None, None, None)

@@ -3,13 +3,13 @@ reference-compatible modules in ganet_amd.modules.GANet are unchanged."""
 import torch
 from torch.nn.modules.module import Module
 
-from ..functions.fused import (DisparityLossFunction, LgaRegressFunction, NormDisparityRegressionFunction, ResidualReluFunction,
+from ..functions.fused import (BnApplyFunction, BnReluFunction, DisparityLossFunction, LgaRegressFunction, NormDisparityRegressionFunction, ResidualReluFunction,
                                SoftminDisparityRegressionFunction, SoftminFunction, TrilinearUpsampleFunction,
                                disparity_loss_workspace, normalize_filters, normalize_guidance, sga_forward_infer)
 from ..functions.GANet import Lga2Function, LgaFunction, SgaFunction
 
 __all__ = ["GuidedSGA", "GuidedSGABnRelu", "NormalizedLGA2", "NormDisparityRegression", "SoftminDisparityRegression",
-           "DispAggTail", "TrilinearUpsample", "ResidualBnRelu", "DisparityLoss", "folded_bn"]
+           "DispAggTail", "TrilinearUpsample", "ResidualBnRelu", "DisparityLoss", "folded_bn", "BnRelu", "bn_relu_path"]
 
 
 def folded_bn(bn, refresh=False):
@@ -97,6 +97,69 @@ class ResidualBnRelu(Module):
             inplace = self.inplace and not (torch.is_grad_enabled() and t.requires_grad and t.is_leaf)
             return ResidualReluFunction.apply(t, rem, *folded_bn(bn), inplace)
         return ResidualReluFunction.apply(bn(t), rem, None, None, True)     # bn(t) is a temporary of this call: always in place
+
+
+def bn_relu_path(bn, x, rem=None):
+    """Which way BnRelu(bn) takes for these inputs -- decided on the host from types and flags alone:
+      "train"      batch statistics (training mode, or track_running_stats=False): the native training kernels
+      "fold"       eval mode with frozen statistics: folded_bn(bn) and the one-pass apply kernel
+      "framework"  bn(x) in PyTorch followed by the add and the ReLU: eval mode where the BatchNorm's parameters want
+                   gradients; momentum=None (the cumulative average needs a host read of the batch counter); tensors that
+                   are not fp32 on a HIP device; a SyncBatchNorm while a process group of more than one rank is initialised
+                   (its statistics need a collective between the partial sums and the finishing step)"""
+    ts = [x] + ([rem] if rem is not None else []) + [t for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var) if t is not None]
+    if any(not t.is_cuda or t.dtype != torch.float32 or t.device != x.device for t in ts) or x.dim() < 3:
+        return "framework"
+    if bn.training or not bn.track_running_stats:
+        if bn.track_running_stats and bn.momentum is None:
+            return "framework"
+        if isinstance(bn, torch.nn.SyncBatchNorm) and torch.distributed.is_available() and torch.distributed.is_initialized() \
+                and torch.distributed.get_world_size() > 1:
+            return "framework"
+        return "train"
+    if torch.is_grad_enabled() and any(p.requires_grad for p in bn.parameters()):
+        return "framework"
+    return "fold"
+
+
+class BnRelu(Module):
+    """`bn` + optional residual + optional ReLU as one op: forward(x, rem=None) == relu(bn(x) + rem) for the
+    `conv -> bn -> F.relu(inplace=True)` of every BasicConv (models/GANet_deep.py:35-41; the caller passes x = conv(..)) and
+    for SGABlock's tail (:270-277), for BatchNorm2d and BatchNorm3d.
+
+    Training mode: batch statistics, running-stat update and normalise + add + ReLU in two launches forward and two
+    backward (stock PyTorch: about 5 volume passes forward and 8 backward, here 3 and 5); the output is not kept for the
+    backward.  Eval mode with frozen statistics: the folded affine, the add and the ReLU in one pass, in place under no_grad.
+    Everything else goes to the framework: see bn_relu_path."""
+
+    def __init__(self, bn, relu=True, inplace=True):
+        super().__init__()
+        if not isinstance(bn, torch.nn.modules.batchnorm._BatchNorm):
+            raise TypeError("BnRelu wraps a BatchNorm2d / BatchNorm3d")
+        self.bn = bn                      # the caller's BatchNorm (shared, not copied)
+        self.relu = relu
+        self.inplace = inplace            # eval mode under no_grad: y overwrites x (x: the convolution's output, a temporary)
+
+    def forward(self, x, rem=None):
+        bn = self.bn
+        path = bn_relu_path(bn, x, rem)
+        if path == "framework":
+            t = bn(x)
+            if rem is not None and self.relu and t.is_cuda and t.dtype == torch.float32 and t.dim() == 5:
+                return ResidualReluFunction.apply(t.contiguous(), rem.contiguous(), None, None, True)
+            if rem is not None:
+                t = t + rem
+            return torch.relu(t) if self.relu else t
+        x = x.contiguous()
+        rem = rem.contiguous() if rem is not None else None
+        if path == "fold":
+            # in place only where nothing can ask for the overwritten values again
+            return BnApplyFunction.apply(x, rem, *folded_bn(bn), self.relu, self.inplace and not torch.is_grad_enabled())
+        if bn.training and bn.track_running_stats and bn.num_batches_tracked is not None:
+            bn.num_batches_tracked.add_(1)          # as the module does; folded_bn sees the statistics change through it
+        running = (bn.running_mean, bn.running_var) if bn.training and bn.track_running_stats else (None, None)
+        return BnReluFunction.apply(x, rem, bn.weight, bn.bias, *running, bn.momentum if bn.momentum is not None else 0.0,
+                                    bn.eps, self.relu)
 
 
 class NormalizedLGA2(Module):

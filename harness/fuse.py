@@ -9,12 +9,16 @@ rebinding `forward` on the SGABlock / DispAgg / Disp instances.
   Disp.forward      models/GANet_deep.py:213-219   after the upsampling: Softmin + regression -> SoftminDisparityRegression
   both tails        models/GANet_deep.py:212, 240  F.interpolate(trilinear) -> TrilinearUpsample (gather backward instead of
                                                    ATen's atomics: 22.5 ms of a 114 ms training step, profiles/r2_model_train_stock.json)
+use_fused_bn (opt-in on top, or alone):
+  BasicConv.forward models/GANet_deep.py:35-41     conv -> bn -> F.relu(inplace=True): BatchNorm (batch statistics in training
+                                                   mode, folded in eval mode) and ReLU -> BnRelu; the convolution stays MIOpen's
+  SGABlock's tail   models/GANet_deep.py:270-277   where use_fused_ops has put a ResidualBnRelu: -> BnRelu(bn)(t, rem)
 """
 import types
 
 import torch
 
-from ganet_amd.modules.fused import (DispAggTail, GuidedSGA, GuidedSGABnRelu, ResidualBnRelu, SoftminDisparityRegression,
+from ganet_amd.modules.fused import (BnRelu, DispAggTail, GuidedSGA, GuidedSGABnRelu, ResidualBnRelu, SoftminDisparityRegression,
                                      TrilinearUpsample)
 
 _UP = TrilinearUpsample()
@@ -63,5 +67,26 @@ def use_fused_ops(model):
         elif kind == "Disp":
             object.__setattr__(m, "_fused_tail", SoftminDisparityRegression(m.maxdisp))
             m.forward = types.MethodType(_disp_forward, m)
+            n += 1
+    return n
+
+
+def _basicconv_forward(self, x):
+    return self._fused_bn(self.conv(x))       # bn + relu (models/GANet_deep.py:37-40) in BnRelu's passes
+
+
+def use_fused_bn(model):
+    """BatchNorm + ReLU behind every BasicConv with use_bn, and the tails use_fused_ops has rebound, on BnRelu.  Call it
+    after use_fused_ops where both are wanted.  Returns the number of call sites rebound."""
+    n = 0
+    for m in model.modules():
+        kind = type(m).__name__
+        if kind == "BasicConv" and m.use_bn:
+            # (object.__setattr__: the helper stays out of the module tree, state_dict keys do not move)
+            object.__setattr__(m, "_fused_bn", BnRelu(m.bn, relu=bool(m.relu)))
+            m.forward = types.MethodType(_basicconv_forward, m)
+            n += 1
+        elif kind == "SGABlock" and isinstance(m.__dict__.get("_fused_tail"), ResidualBnRelu):
+            object.__setattr__(m, "_fused_tail", BnRelu(m._fused_tail.bn, relu=True))      # the same call form (t, rem)
             n += 1
     return n

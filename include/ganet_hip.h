@@ -35,7 +35,7 @@ extern "C" {
 #define GANET_E_UNSUPPORTED (-2)  /* shape outside the compiled kernel set         */
 #define GANET_E_RUNTIME (-3)      /* HIP runtime / launch error                    */
 
-#define GANET_ABI_VERSION 12      /* v12 = v11 + ganet_disparity_loss_workspace / _forward / _backward (the training criterion) */
+#define GANET_ABI_VERSION 13      /* v13 = v12 + ganet_bn_workspace / _train_forward / _train_backward / _apply_forward (BatchNorm + ReLU) */
 int ganet_abi_version(void);
 const char *ganet_last_error(void);
 /* 1 if this build runs the lockstep CPU emulator (tests only), 0 for the gfx950 build */
@@ -309,6 +309,40 @@ int ganet_disparity_loss_backward(const float *p0, const float *p1, const float 
                                   const float *params, const float *stats, const float *grad_loss,
                                   float *g0, float *g1, float *g2,
                                   int N, int H, int W, int P, int kind0, int kind1, int kind2, int mask_mode, void *stream);
+
+/* ---------------------------------------------------------------- batch norm ----- */
+
+/* ABI v13.  Training-mode BatchNorm + optional residual + optional ReLU on fp32 [N, C, S] (S = D*H*W or H*W, contiguous
+ * slices), two launches each way, no atomics, no host round trip; two runs are bit-identical.
+ *   statistics   per channel over M = N*S values, sums in fp64: mean, biased var, invstd = 1/sqrt(var + eps); mean and invstd
+ *                rounded to fp32 once (save_mean, save_invstd [C]);  scale = weight * invstd, shift = fmaf(-mean, scale, bias)
+ *                (weight / bias NULL: 1 / 0)
+ *   running      running_mean = (1-m) running_mean + m mean, running_var = (1-m) running_var + m var M/(M-1), in fp64 from the
+ *                unrounded statistics, written exactly once per channel; both NULL: no update
+ *   forward      z = fmaf(x, scale, shift) [+ rem],  y = relu ? (z <= 0 ? 0 : z) : z   (a NaN passes through)
+ *   backward     g = relu && z <= 0 ? 0 : grad_y, the mask recomputed from x (and rem): y is never read;
+ *                grad_bias = sum g, grad_weight = invstd * sum g (x - mean), grad_rem = g,
+ *                grad_x = scale * (g - k1 - (x - mean) q), k1 = sum g / M, q = invstd^2 sum g (x - mean) / M.
+ *                A NULL output is not computed.
+ * momentum_bits / eps_bits: the two fp32 values as their bit patterns (the ABI's scalars are ints).  relu: 0 | 1.
+ * workspace: ganet_bn_workspace(N, C, S) doubles, private to the call until it has run; forward and backward may share one.
+ * y, grad_x and grad_rem must not alias an input.  16-byte requests where S % 4 == 0 and every base is 16-byte aligned.
+ * M = 1, NULL x, non-positive sizes: GANET_E_INVALID.  C > 65535: GANET_E_UNSUPPORTED.  M up to 2^40 and beyond (64-bit offsets).
+ * ganet_bn_apply_forward is the eval form: y = relu(scale[c] x + shift[c] [+ rem]) with the BatchNorm folded from its running
+ * statistics into (scale, shift) [C]; here y may alias x.
+ * Replaces: models/GANet_deep.py:35-41 (BasicConv.forward: `bn` and F.relu(inplace=True) behind the convolution) and
+ *           :270-277 (SGABlock's tail: conv_refine's BatchNorm3d, `x += rem`, relu), with their autograd backward. */
+int ganet_bn_workspace(int N, int C, int S);
+int ganet_bn_train_forward(const float *x, const float *rem, const float *weight, const float *bias,
+                           float *running_mean, float *running_var, double *workspace, float *y,
+                           float *save_mean, float *save_invstd,
+                           int N, int C, int S, int momentum_bits, int eps_bits, int relu, void *stream);
+int ganet_bn_train_backward(const float *x, const float *rem, const float *grad_y, const float *weight, const float *bias,
+                            const float *save_mean, const float *save_invstd, double *workspace,
+                            float *grad_x, float *grad_rem, float *grad_weight, float *grad_bias,
+                            int N, int C, int S, int relu, void *stream);
+int ganet_bn_apply_forward(const float *x, const float *rem, const float *scale, const float *shift, float *y,
+                           int N, int C, int S, int relu, void *stream);
 
 /* ---------------------------------------------------------------- diagnostics ---- */
 
