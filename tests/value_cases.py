@@ -85,10 +85,10 @@ def bn_relu_exact(v, scale, shift):
     return np.maximum(s, 0).astype(np.float32)
 
 
-def run_sga_infer(api, dev, oracle, family, shape, with_bn):
-    """ganet_sga_forward_infer (running maximum, no mask): `out` equal to the oracle's, through the folded BN + ReLU epilogue
+def check_sga_infer(api, dev, x, gs, want_out, with_bn):
+    """ganet_sga_forward_infer (running maximum, no mask): `out` equal to want_out, through the folded BN + ReLU epilogue
     (dyadic scale / shift) as well."""
-    x, gs, go, want = sga_case(oracle, family, shape)
+    shape = x.shape
     N, C, D, H, W = shape
     scale = np.array([0.5, 1.5, -0.75, 2.0], np.float32)[:C]
     shift = np.array([0.25, -1.0, 0.5, -0.125], np.float32)[:C]
@@ -98,9 +98,15 @@ def run_sga_infer(api, dev, oracle, family, shape, with_bn):
     api.call("ganet_sga_forward_infer", dev.ptr(dx), *[dev.ptr(g) for g in dg], dev.ptr(A), dev.ptr(out),
              dev.ptr(ds) if with_bn else None, dev.ptr(dt) if with_bn else None, N, C, D, H, W, dev.stream)
     dev.sync()
-    exp = bn_relu_exact(want["out"], scale, shift) if with_bn else want["out"]
+    exp = bn_relu_exact(want_out, scale, shift) if with_bn else want_out
     got = dev.host(out)
     assert np.array_equal(got, exp), (int((got != exp).sum()), float(np.abs(got - exp).max()))
+
+
+def run_sga_infer(api, dev, oracle, family, shape, with_bn):
+    """check_sga_infer on the family's inputs with the oracle's `out`"""
+    x, gs, go, want = sga_case(oracle, family, shape)
+    check_sga_infer(api, dev, x, gs, want["out"], with_bn)
 
 
 # ---- LGA ------------------------------------------------------------------------------------------------------------------
