@@ -25,7 +25,9 @@ def _b(v):
 
 
 class Reference:
-    def __init__(self, x, rem, grad_y, weight, bias, running_mean, running_var, momentum, eps, relu):
+    def __init__(self, x, rem, grad_y, weight, bias, running_mean, running_var, momentum, eps, relu, relu_positive=None):
+        """relu_positive (recorded data, which nobody can nudge away from the kink): a boolean array that decides the ReLU at
+        the elements where float64 cannot speak for fp32 -- undecided(), |z| <= 4 B_y; everywhere else z decides as always"""
         with np.errstate(all="ignore"):
             x = np.asarray(x, F32)
             N, C, S = x.shape
@@ -44,8 +46,11 @@ class Reference:
             self.invstd = 1.0 / np.sqrt(self.var + self.eps)
             self.scale = self.weight * self.invstd
             self.z = self.xm * _b(self.scale) + _b(self.bias) + self.rem
-            self.y = np.where(self.z <= 0, 0.0, self.z) if self.relu else self.z
-            self.g = np.where(self.z <= 0, 0.0, self.gy) if self.relu else self.gy
+            off = self.z <= 0
+            if self.relu and relu_positive is not None:
+                off = np.where(self.undecided(), ~np.asarray(relu_positive, bool).reshape(x.shape), off)
+            self.y = np.where(off, 0.0, self.z) if self.relu else self.z
+            self.g = np.where(off, 0.0, self.gy) if self.relu else self.gy
             self.sum_g = _per_channel(self.g)
             self.sum_gxm = _per_channel(self.g * self.xm)
             self.sum_abs_g = _per_channel(np.abs(self.g))
@@ -69,11 +74,16 @@ class Reference:
     def bar_y(self):
         return 2.0 ** -21 * ((np.abs(self.x) + _b(np.abs(self.mean))) * _b(np.abs(self.scale)) + _b(np.abs(self.bias)) + np.abs(self.rem))
 
-    def bar_grad_x(self):
+    def bar_grad_x(self, mean_term=False):
+        """mean_term (bn_cases: the far-mean cases and recorded model data): the rounding of the saved mean, 2^-24 |mean|, also
+        sits in sum g (x - mean) and so in q -- |xhat| invstd |k1| times it, with the factor 4 of the bars' other terms"""
         xhat = self.xm * _b(self.invstd)
         qt = self.grad_weight / F64(self.M)
-        return _b(np.abs(self.scale)) * (2.0 ** -20 * (np.abs(self.g) + _b(np.abs(self.k1)) + np.abs(xhat * _b(qt))) +
-                                         2.0 ** -23 * _b(np.abs(self.mean) * self.invstd * np.abs(qt)))
+        bar = _b(np.abs(self.scale)) * (2.0 ** -20 * (np.abs(self.g) + _b(np.abs(self.k1)) + np.abs(xhat * _b(qt))) +
+                                        2.0 ** -23 * _b(np.abs(self.mean) * self.invstd * np.abs(qt)))
+        if mean_term:
+            bar = bar + _b(np.abs(self.scale)) * 2.0 ** -22 * np.abs(xhat) * _b(np.abs(self.mean) * self.invstd * np.abs(self.k1))
+        return bar
 
     def undecided(self):
         """elements whose ReLU mask the fp32 arithmetic may decide the other way: |z| <= 4 B_y.  (A z that is exactly zero

@@ -29,45 +29,116 @@ def _taps(r, D, H, W):
                 yield t, tuple(dst), tuple(src)
 
 
-def lga_forward(x, f, r):
+MUTATIONS = ("drop_tap", "zero_pad")                    # private switches of lga_forward / lga_backward: see mutated_chain()
+
+
+def _dropped(t, r, _mut):
+    """"drop_tap" leaves out the tap (dd, a, b') = (0, 0, +1): the centre plane's right-hand neighbour"""
+    ws = 2 * r + 1
+    return _mut == "drop_tap" and t == ws * ws + r * ws + r + 1
+
+
+def lga_forward(x, f, r, _mut=None):
+    assert _mut is None or _mut in MUTATIONS
     xs, fs = _fold(x, f)
     B, D, H, W = xs.shape
     y = np.zeros_like(xs)
     for t, dst, src in _taps(r, D, H, W):
-        v = xs.copy()                                     # outside: the centre value
+        if _dropped(t, r, _mut):
+            continue
+        v = np.zeros_like(xs) if _mut == "zero_pad" else xs.copy()      # outside: the centre value
         v[(slice(None),) + dst] = xs[(slice(None),) + src]
         y += fs[:, t][:, None] * v
     return y.reshape(x.shape)
 
 
-def lga_backward(x, f, gy, r):
+def lga_backward(x, f, gy, r, _mut=None):
     """-> (gx, gf): the adjoints of lga_forward in x and in f"""
+    assert _mut is None or _mut in MUTATIONS
     xs, fs = _fold(x, f)
     gs = gy.reshape(xs.shape).astype(np.float64)
     B, D, H, W = xs.shape
     gx, gf = np.zeros_like(xs), np.zeros_like(fs)
     for t, dst, src in _taps(r, D, H, W):
-        v = xs.copy()
+        if _dropped(t, r, _mut):
+            continue
+        v = np.zeros_like(xs) if _mut == "zero_pad" else xs.copy()
         v[(slice(None),) + dst] = xs[(slice(None),) + src]
         gf[:, t] = (gs * v).sum(1)
         c = fs[:, t][:, None] * gs                        # what each output position hands to the element it read
-        inside = np.zeros((D, H, W), bool)
-        inside[dst] = True
-        gx += np.where(inside, 0.0, c)                    # ... the centre, where the tap left the volume
+        if _mut != "zero_pad":
+            inside = np.zeros((D, H, W), bool)
+            inside[dst] = True
+            gx += np.where(inside, 0.0, c)                # ... the centre, where the tap left the volume
         gx[(slice(None),) + src] += c[(slice(None),) + dst]
     return gx.reshape(x.shape), gf.reshape(f.shape)
 
 
-def lga_chain(x, f, gy, r, passes):
+def lga_chain(x, f, gy, r, passes, _mut=None):
     """`passes` chained passes with one filter tensor and their backward: -> dict(y, gx, gf, ins=[input of each pass])"""
     ins = [np.asarray(x, np.float64)]
     for _ in range(passes):
-        ins.append(lga_forward(ins[-1], f, r))
+        ins.append(lga_forward(ins[-1], f, r, _mut))
     g, gf = np.asarray(gy, np.float64), 0.0
     for xin in reversed(ins[:-1]):
-        g, gfk = lga_backward(xin, f, g, r)
+        g, gfk = lga_backward(xin, f, g, r, _mut)
         gf = gf + gfk
     return {"y": ins[-1], "gx": g, "gf": gf, "ins": ins[:-1]}
+
+
+def mutated_chain(x, f, gy, r, passes, what):
+    """lga_chain with one thing wrong, for the tests that show that a comparison notices:  "drop_tap" -- every pass and its
+    adjoints lack one of the 3(2r+1)^2 taps;  "zero_pad" -- a tap that leaves the volume reads 0 instead of the centre value."""
+    assert what in MUTATIONS
+    return lga_chain(x, f, gy, r, passes, what)
+
+
+U = 2.0 ** -24
+
+
+def _gamma(n):
+    return n * U / (1.0 - n * U)
+
+
+def chain_bound(x, f, gy, r, passes):
+    """A first-order rounding-error bound, per element, for an fp32 evaluation of lga_chain: -> dict(y, gx, gf) of bounds, and
+    `want`, the float64 chain they belong to.  Whoever compares allows a factor 2 for the second-order terms, as with SGA.
+
+    u = 2^-24.  A sum of n rounded products, accumulated in any order (fused or not, split over lanes or not), differs from
+    the exact sum of the same terms by at most gamma_n sum|terms|, gamma_n = n u / (1 - n u) (every term passes through at
+    most n roundings: its product and at most n - 1 additions).  To first order the error of a computed quantity is what its
+    inputs' errors contribute through the exact (linear) formula, plus that.  x, f and gy are exact fp32 inputs.
+
+      forward   x_0 = x, x_{k+1}[p] = sum_t f_t[p] v_t(x_k)[p], T = 3(2r+1)^2 terms (v_t: the tap, or the centre value):
+                    E_0 = 0,   E_{k+1} = sum_t |f_t| v_t(E_k) + gamma_T sum_t |f_t| |v_t(x_k)|
+                -- the previous pass's bound pushed through |f|, plus gamma_T times the absolute-value sum of the element's
+                own accumulation.  Both are lga_forward on absolute values.
+      data      g_P = gy, g_k = adjoint of pass k applied to g_{k+1}.  An element q receives one term f_t[q-o] g[q-o] from
+      adjoint   every tap whose reader q - o lies inside the volume, and one term f_t[q] g[q] from every tap of its OWN pixel
+                that leaves the volume at q + o; the tap set is symmetric (o <-> -o), so these are T terms altogether:
+                    G_P = 0,   G_k = adj(|f|, G_{k+1}) + gamma_T adj(|f|, |g_{k+1}|)
+                (a kernel that first sums the out-of-range filters of a pixel and multiplies once stays inside: T - 1 roundings).
+      filter    gf_t[p] = sum_k sum_d g_{k+1}[d,p] v_t(x_k)[d,p]: per pass D products, and the passes' results added up --
+      gradient  n = D + passes roundings at most on any term's way; both factors carry their own bounds:
+                    E = sum_k sum_d (G_{k+1} |v_t(x_k)| + |g_{k+1}| v_t(E_k)) + gamma_n sum_k sum_d |g_{k+1} v_t(x_k)|
+                Each of the three sums is the filter gradient of lga_backward on absolute values.
+
+    Everything is computed from the float64 chain beside it, from the inputs alone."""
+    fa = np.abs(np.asarray(f, np.float64))
+    T, D = f.shape[-3], x.shape[-3]
+    want = lga_chain(x, f, gy, r, passes)
+    gT, gN = _gamma(T), _gamma(D + passes)
+    E = [np.zeros(x.shape)]
+    for k in range(passes):
+        E.append(lga_forward(E[k], fa, r) + gT * lga_forward(np.abs(want["ins"][k]), fa, r))
+    g, G, egf = np.asarray(gy, np.float64), np.zeros(x.shape), 0.0
+    for k in reversed(range(passes)):
+        xk = np.abs(want["ins"][k])
+        through, own = lga_backward(xk, fa, G, r), lga_backward(xk, fa, np.abs(g), r)
+        egf = egf + through[1] + lga_backward(E[k], fa, np.abs(g), r)[1] + gN * own[1]
+        G = through[0] + gT * own[0]
+        g = lga_backward(want["ins"][k], f, g, r)[0]
+    return {"y": E[passes], "gx": G, "gf": egf, "want": want}
 
 
 def assert_lga_exact_by_norms(x, f, gy, r, passes):

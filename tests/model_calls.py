@@ -1,0 +1,640 @@
+"""TEST INFRASTRUCTURE: every guided-aggregation op call of a MODEL run, held to the float64 statement of its operation --
+shared by tests/test_model_calls_cpu.py (the CPU-oracle twin: the yardstick alone, and its teeth) and
+tests/test_gpu_model_calls.py (the product, call by call).
+
+Why: the per-op case tables feed inputs of magnitude about 1 and hold gradients to parity_cases.TOL = 1e-4 ABSOLUTE; a model
+drives the ops with gradients of 1e-2 .. 1e-4, where that bar lets an all-zero LGA2 data gradient through.  The float64
+statements (sga_ref64, lga_ref64.chain_bound, misc_ref64, bn_ref64, loss_ref64) scale with the data, so they are applied
+here to the tensors a model run really hands to each op.
+
+`recording` wraps forward / backward of a list of autograd Functions (and plain launch functions) for its duration and keeps
+one `Record` per call: kind, arguments (host copies of the tensors, cloned BEFORE the call), outputs, incoming and returned
+gradients, SgaFunction's saved A / mask / kp, and every input that was written.  `check_all(records, oracle)` runs each
+record through the checker of its kind and FAILS, naming the kinds, if a recorded call has none: no op call of a model run
+goes unexamined.
+
+The checkers evaluate the statements on the RECORDED inputs (which came from the device), never on regenerated ones.  SGA
+and LGA are split in two -- `*_reference(record)` (the expensive float64 side, computed once) and `*_judge(reference, got)`
+-- so that the CPU test can hand the same reference results that are wrong on purpose.
+
+Absolute bars of the case tables (misc_cases: `atol`) belong to data of magnitude about 1 (randn, dyadic grids).  The absolute
+error of an fp32 operation scales with its data, down as well as up -- an absolute bar below one ulp of the data cannot be
+met by any fp32 code, and one far above the data checks nothing -- so on recorded data the bar becomes
+atol * max |float64 result| of that output (`_atol`).  The regressions' outputs are in disparity units: their 1e-4 was set for
+disparities up to 192 and becomes 1e-4 * (D - 1) / 192 (`_atol_px`).  The relative parts (`rtol`) stay as they are."""
+import collections
+import contextlib
+import inspect
+
+import numpy as np
+import torch
+
+import bn_cases
+import bn_ref64
+import lga_ref64
+import loss_cases
+import loss_ref64
+import misc_cases as mc
+import misc_ref64 as m64
+import sga_ref64_cases as sc
+import value_cases as vc
+
+U = 2.0 ** -24
+FACTOR = sc.FACTOR                      # the project's allowance for the second-order terms of a first-order bound
+ONE_ROUNDING = U * (1 + 2.0 ** -20)     # |fl32(s) - s| <= u |s|; the margin covers the float64 evaluation of s itself
+
+
+# ---- the recorder ---------------------------------------------------------------------------------------------------------------
+class Record:
+    """one op call.  args: the call's positional arguments in order, tensors as host arrays cloned before the call;
+    outputs / grad_out / grad_in: lists of host arrays (None where autograd passed or got None); saved: name -> array;
+    written: [(phase, what)] -- every input (or incoming gradient) whose values differ after the phase from before it"""
+
+    def __init__(self, kind, args, needs_grad):
+        self.kind, self.args, self.needs_grad = kind, args, needs_grad
+        self.outputs, self.grad_out, self.grad_in, self.saved, self.written = None, None, None, {}, []
+        self.live, self.after, self.reference = None, {}, None
+
+    def __repr__(self):
+        shapes = [tuple(a.shape) for a in self.args if isinstance(a, np.ndarray)]
+        return f"{self.kind}{shapes}"
+
+
+def _host(t):
+    return t.detach().cpu().numpy().copy() if isinstance(t, torch.Tensor) else t
+
+
+def _seq(v):
+    return list(v) if isinstance(v, (tuple, list)) else [v]
+
+
+def _same(t, before):
+    now = t.detach().cpu().numpy()
+    return now.shape == before.shape and now.dtype == before.dtype and now.tobytes() == before.tobytes()      # bits: a NaN is itself
+
+
+def _changed(tensors, before, phase, prefix, record):
+    """notes what was written; -> index -> the values found afterwards"""
+    after = {}
+    for i, (t, b) in enumerate(zip(tensors, before)):
+        if isinstance(t, torch.Tensor) and not _same(t, b):
+            record.written.append((phase, f"{prefix}{i}"))
+            after[i] = _host(t)
+    return after
+
+
+def _wrap_function(patch, records, cls):
+    fwd, bwd, kind = cls.forward, cls.backward, cls.__name__
+
+    def forward(ctx, *args):
+        r = Record(kind, [_host(a) for a in args], any(getattr(ctx, "needs_input_grad", ())))
+        out = fwd(ctx, *args)
+        r.outputs = [_host(o) for o in _seq(out)]
+        r.after = _changed(args, r.args, "forward", "arg", r)
+        r.live = [a for a in args if isinstance(a, torch.Tensor)]
+        ctx._model_call = r
+        records.append(r)
+        return out
+
+    def backward(ctx, *grads):
+        r = ctx._model_call
+        r.grad_out = [_host(g) for g in grads]
+        if kind == "SgaFunction" and not ctx.recompute:
+            A, mask, kp = ctx.saved_tensors[5:8]
+            r.saved = {"A": _host(A), "mask": _host(mask), "kp": _host(kp).view(np.uint16)}
+        elif kind == "SgaFunction":
+            tmp, mask = ctx.saved_tensors[5:7]
+            r.saved = {"tmp": _host(tmp), "mask": _host(mask)}
+        # (between forward and backward other ops may legitimately write an input -- BatchNorm's running statistics on the
+        # next call of a shared module -- so the backward is compared with what it found, not with the forward's clones)
+        before = [_host(t) for t in r.live]
+        res = bwd(ctx, *grads)
+        r.grad_in = [_host(g) if isinstance(g, torch.Tensor) else None for g in _seq(res)]
+        _changed(r.live, before, "backward", "tensor", r)
+        _changed(grads, r.grad_out, "backward", "grad_out", r)
+        return res
+
+    patch.setattr(cls, "forward", staticmethod(forward))
+    patch.setattr(cls, "backward", staticmethod(backward))
+
+
+def _wrap_plain(patch, records, owners, name):
+    orig = getattr(owners[0], name)
+    sig = inspect.signature(orig)
+
+    def call(*args, **kw):
+        bound = sig.bind(*args, **kw)
+        bound.apply_defaults()
+        vals = list(bound.arguments.values())
+        r = Record(name, [_host(a) for a in vals], False)
+        out = orig(*args, **kw)
+        r.outputs = [_host(o) for o in _seq(out)]
+        _changed(vals, r.args, "forward", "arg", r)
+        records.append(r)
+        return out
+
+    for owner in owners:
+        assert getattr(owner, name) is orig, (owner, name)
+        patch.setattr(owner, name, call)
+
+
+@contextlib.contextmanager
+def recording(monkeypatch, functions, plain=()):
+    """functions: autograd Function classes; plain: (modules that hold the name, name) of functions that launch a kernel without
+    a Function.  Yields the list the records are appended to; nothing stays patched afterwards (pytest's monkeypatch)."""
+    records = []
+    with monkeypatch.context() as patch:
+        for cls in dict.fromkeys(functions):
+            _wrap_function(patch, records, cls)
+        for owners, name in plain:
+            _wrap_plain(patch, records, owners, name)
+        yield records
+
+
+def product_functions():
+    """everything in ganet_amd.functions.GANet.__all__, every Function of ganet_amd.functions.fused, and the two plain
+    functions that launch a kernel without one"""
+    import ganet_amd.functions.fused as ff
+    import ganet_amd.functions.GANet as fg
+    import ganet_amd.modules.fused as mf
+    fns = [getattr(fg, n) for n in fg.__all__]
+    fns += [v for v in vars(ff).values() if isinstance(v, type) and issubclass(v, torch.autograd.Function) and v.__module__ == ff.__name__]
+    return fns, [((fg, ff), "_sga_infer"), ((ff, mf), "sga_forward_infer")]
+
+
+def run_product(monkeypatch, name, crop, max_disp, device, fused_ops=False, fused_bn=False, seed=0):
+    """The product model (harness.steps.build_model on the drop-in `libs/`, optionally with harness.fuse's call sites) under
+    the recorder: steps.predict under no_grad, then one training step -- steps.loss_mix on the stock call forms, the fused
+    DisparityLoss on the fused ones.  crop = (H, W, B).  -> (records of predict, records of the training step)"""
+    from ganet_amd.modules.fused import DisparityLoss
+    from harness import fuse, steps
+    H, W, B = crop
+    torch.manual_seed(seed)
+    model = steps.build_model(name, max_disp, device)
+    if fused_ops:
+        assert fuse.use_fused_ops(model) > 0
+    if fused_bn:
+        assert fuse.use_fused_bn(model) > 0
+    left, right, target = steps.synthetic_batch(B, H, W, max_disp, device)
+    with recording(monkeypatch, *product_functions()) as records:
+        steps.predict(model, left, right)
+        n_infer = len(records)
+        model.train()
+        outs = model(left, right)
+        if fused_ops:
+            loss, _ = DisparityLoss.for_model(name, max_disp)(outs, target)
+        else:
+            loss = steps.loss_mix(name, outs, target, target < max_disp, steps.criterion(True))
+        loss.backward()
+    return records[:n_infer], records[n_infer:]
+
+
+def oracle_functions():
+    from oracle.cpu_ops import OracleLgaChain, OracleSga
+    return [OracleSga, OracleLgaChain], []
+
+
+# what an op's own docstring declares written, kind -> record -> names of `args`: the in-place forms (`inplace=True`), the running
+# statistics, an output that is passed in, scratch
+DECLARED = {
+    "ResidualReluFunction": lambda r: {"arg0"} if r.args[4] else set(),        # y overwrites t
+    "BnApplyFunction": lambda r: {"arg0"} if r.args[5] else set(),             # y overwrites x
+    "BnReluFunction": lambda r: {"arg4", "arg5"},                              # running_mean / running_var, as F.batch_norm does
+    "_sga_infer": lambda r: {"arg5"},                                          # `output`
+    "DisparityLossFunction": lambda r: {"arg2"},                               # the fp64 workspace
+}
+
+
+def undeclared_writes(records):
+    """[(index, kind, phase, what)] of every written input that its op does not declare consumed.  Nothing may be written in
+    a backward, and an incoming gradient never."""
+    bad = []
+    for i, r in enumerate(records):
+        allowed = DECLARED.get(r.kind, lambda r: set())(r)
+        for phase, what in r.written:
+            if phase != "forward" or what not in allowed:
+                bad.append((i, r.kind, phase, what))
+    return bad
+
+
+# ---- helpers ----------------------------------------------------------------------------------------------------------------------
+def _ratio(err, bound):
+    """largest err / bound over the elements (an element whose bound is 0 must be met exactly)"""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        q = np.where(err == 0, 0.0, err / bound)
+    return float(np.max(q, initial=0.0))
+
+
+def _within(name, got, want, bound, factor=1.0):
+    got, want = np.asarray(got), np.asarray(want, np.float64)
+    assert got.shape == want.shape, (name, got.shape, want.shape)
+    assert np.isfinite(got).all(), (name, "not finite")
+    q = _ratio(np.abs(got.astype(np.float64) - want), np.broadcast_to(bound, want.shape))
+    assert q <= factor, (name, f"error / bound = {q:.4g} > {factor}")
+    return q
+
+
+def _atol(atol, want, where=None):
+    v = np.abs(np.asarray(want, np.float64))
+    if where is not None:
+        v = v[where]
+    return atol * float(v.max(initial=0.0))
+
+
+def _atol_px(atol, D):
+    return atol * (D - 1) / 192.0
+
+
+def _close(name, got, want, rtol, atol, rel_only=None, px=None):
+    """misc_cases' "close" with its absolute part restated (module docstring) -> the largest error / (atol' + rtol |want|).
+    px: the output is in disparity units, of a volume with that many disparities"""
+    keep = None if rel_only is None or not rel_only.any() else ~np.broadcast_to(rel_only, np.shape(want))
+    a = _atol(atol, want, keep) if px is None else _atol_px(atol, px)
+    mc.check([mc.Cmp(name, np.asarray(got), want, "close", rtol, a, rel_only=rel_only if keep is not None else None)])
+    w = np.asarray(want, np.float64)
+    return _ratio(np.abs(np.asarray(got, np.float64) - w), a + rtol * np.abs(w))
+
+
+# ---- SGA ------------------------------------------------------------------------------------------------------------------------
+def _sga_inputs(r):
+    a = r.args[1:6] if r.kind == "OracleSga" else r.args[:5]
+    return a[0], list(a[1:5])
+
+
+def sga_reference(r, oracle):
+    """the oracle on the recorded inputs (out, mask, A0..A3, tmp, kp = first arg-max, gradients) and, where a gradient came in,
+    the float64 statement evaluated on the ORACLE's selections"""
+    x, gs = _sga_inputs(r)
+    if r.grad_out is None:
+        return {"want": {"out": oracle.sga_forward(x, *gs)[0]}, "ref": None}
+    go = r.grad_out[0]
+    want = sc.oracle_results(oracle, x, gs, go)
+    return {"want": want, "ref": sc.ref64(x, gs, go, kp=want["kp"], mask=want["mask"])}
+
+
+def sga_got(r, R):
+    """what the call produced, under sga_ref64's keys.  OracleSga keeps no volumes: the oracle's own, from `R`"""
+    got = {"out": r.outputs[0]}
+    if r.grad_in is not None:
+        grads = r.grad_in[1:6] if r.kind == "OracleSga" else r.grad_in[:5]
+        got.update(zip(sc.GRADS, grads))
+    if r.kind == "OracleSga":
+        got.update({k: R["want"][k] for k in ("A0", "A1", "A2", "A3", "tmp", "mask", "kp") if k in R["want"]})
+    elif "A" in r.saved:
+        got.update({f"A{d}": r.saved["A"][d] for d in range(4)})
+        got.update(tmp=r.saved["A"][3], mask=r.saved["mask"], kp=r.saved["kp"])
+    elif "tmp" in r.saved:                           # GANET_SGA_SAVE=recompute keeps A_left and a float mask
+        got.update(tmp=r.saved["tmp"], mask=r.saved["mask"])
+    return got
+
+
+def sga_judge(R, got, equality=True, what=""):
+    """out / mask / A / kp EQUAL to the oracle's -- the standing guarantee, on model data -- then forward volumes and all five
+    gradients within FACTOR x sga_ref64's bound of float64 on the oracle's selections.  Only what `got` holds is compared
+    (the no-grad path: out; recompute mode: out, tmp, mask, gradients).  -> key -> error / bound"""
+    want, ref = R["want"], R["ref"]
+    if equality:
+        sc.assert_equal(got, want, [k for k in sc.FWD if k in got and k in want], what)
+        if "mask" in got:
+            assert np.array_equal(np.asarray(got["mask"]).astype(np.uint8), want["mask"]), (what, "mask")
+        if "kp" in got:
+            assert np.array_equal(np.asarray(got["kp"], np.int64), want["kp"]), (what, "kp")
+    if ref is None:
+        return {"out": 0.0}
+    keys = [k for k in sc.FWD + sc.GRADS if k in got]
+    assert all(k in got for k in sc.GRADS), (what, "a gradient is missing")
+    return sc.assert_within_bound(got, ref, keys, what)
+
+
+def reference_of(r, oracle):
+    """the float64 side of an SGA / LGA record, computed once and kept on the record"""
+    if r.reference is None:
+        r.reference = sga_reference(r, oracle) if r.kind in ("SgaFunction", "OracleSga") else lga_reference(r)
+    return r.reference
+
+
+def check_sga(r, oracle):
+    R = reference_of(r, oracle)
+    return sga_judge(R, sga_got(r, R), what=repr(r))
+
+
+def check_sga_infer(r, oracle):
+    """_sga_infer / sga_forward_infer: out equal to the oracle's; through the folded BN + ReLU with value_cases.bn_relu_exact's
+    rule where the float64 sum is exact, else within ONE rounding of relu(scale[c] * out + shift[c]) -- the epilogue is one
+    fma on the exact fp32 `out`, so |got - s| <= u |s| and nothing else"""
+    x, gs = r.args[0], list(r.args[1:5])
+    scale, shift = (r.args[6], r.args[7]) if r.kind == "_sga_infer" else (r.args[5], r.args[6])
+    out = oracle.sga_forward(x, *gs)[0]
+    got = r.outputs[0]
+    if scale is None:
+        sc.assert_equal({"out": got}, {"out": out}, ["out"], repr(r))
+        return {"out": 0.0}
+    try:
+        exp = vc.bn_relu_exact(out, scale, shift)
+    except AssertionError:
+        C = scale.size
+        s = out.astype(np.float64) * scale.astype(np.float64).reshape(1, C, 1, 1, 1) + shift.astype(np.float64).reshape(1, C, 1, 1, 1)
+        assert not (got < 0).any()
+        return {"out": _within("out", got, np.maximum(s, 0.0), ONE_ROUNDING * np.abs(s))}
+    sc.assert_equal({"out": got}, {"out": exp}, ["out"], repr(r))
+    return {"out": 0.0}
+
+
+# ---- LGA chains -----------------------------------------------------------------------------------------------------------------
+LGA_PASSES = {"LgaFunction": 1, "Lga2Function": 2, "Lga3Function": 3, "Lga3dFunction": 1, "Lga3d2Function": 2, "Lga3d3Function": 3}
+LGA_KEYS = ("y", "gx", "gf")
+
+
+def _lga_inputs(r):
+    if r.kind == "OracleLgaChain":
+        return r.args[1], r.args[2], int(r.args[3]), int(r.args[4])
+    return r.args[0], r.args[1], int(r.args[2]) if len(r.args) > 2 else 1, LGA_PASSES[r.kind]
+
+
+def lga_reference(r):
+    """lga_ref64.chain_bound on the recorded x, f and incoming gradient (no gradient came in: zeros, and only y is compared)"""
+    x, f, radius, passes = _lga_inputs(r)
+    gy = r.grad_out[0] if r.grad_out is not None else np.zeros_like(x)
+    return lga_ref64.chain_bound(x, f, gy, radius, passes)
+
+
+def lga_got(r):
+    got = {"y": r.outputs[0]}
+    if r.grad_in is not None:
+        g = r.grad_in[1:3] if r.kind == "OracleLgaChain" else r.grad_in[:2]
+        got.update(gx=g[0], gf=g[1])
+    return got
+
+
+def lga_ratios(R, got):
+    return {k: _ratio(np.abs(np.asarray(got[k], np.float64) - R["want"][k]), R[k]) for k in LGA_KEYS if k in got}
+
+
+def lga_judge(R, got, what=""):
+    """|got - float64| <= FACTOR x chain_bound per element of y, gx and gf -> key -> error / bound"""
+    for k in got:
+        assert np.shape(got[k]) == R["want"][k].shape and np.isfinite(got[k]).all(), (what, k)
+    q = lga_ratios(R, got)
+    assert max(q.values()) <= FACTOR, (what, {k: v for k, v in q.items() if v > FACTOR})
+    return q
+
+
+def check_lga(r, oracle=None):
+    return lga_judge(reference_of(r, oracle), lga_got(r), repr(r))
+
+
+# ---- everything else the fused configurations call ---------------------------------------------------------------------------
+def _gamma(n):
+    return n * U / (1 - n * U)
+
+
+def check_cost_volume(r, oracle=None):
+    """forward: copies and zeros, the same bits.  backward: each gradient is a plain sum of at most Dn fp32 terms -- the case
+    table's EQUAL on integer gradients becomes gamma_Dn sum |terms| on real ones (n terms, n - 1 additions, any order)"""
+    x, y, Dn = r.args
+    mc.check([mc.Cmp("cost", r.outputs[0], m64.cost_volume(x, y, Dn), "bits")])
+    q = {"cost": 0.0}
+    if r.grad_in is not None:
+        g, C = r.grad_out[0], x.shape[1]
+        want, mag = m64.cost_volume_adjoint(g, C), m64.cost_volume_adjoint(np.abs(g), C)
+        for k, i in (("gx", 0), ("gy", 1)):
+            q[k] = _within(k, r.grad_in[i], want[i], _gamma(Dn) * mag[i])
+    return q
+
+
+def check_disparity_regression(r, oracle=None):
+    """out = sum_d d x_d: D products and D - 1 additions, gamma_D sum d |x_d| (the case table's EQUAL holds on its dyadic
+    inputs only); the backward is one product per element: one rounding"""
+    x, Dn = r.args
+    q = {"out": _within("out", r.outputs[0], m64.regression(x), _gamma(Dn) * m64.regression(np.abs(x)))}
+    if r.grad_in is not None:
+        want = m64.regression_adjoint(r.grad_out[0], Dn)
+        q["gx"] = _within("gx", r.grad_in[0], want, ONE_ROUNDING * np.abs(want))
+    return q
+
+
+def check_l1_normalize(r, oracle=None):
+    x, G, C, K = r.args
+    N, _, H, W = x.shape
+    x6 = x.reshape(N, G, C, K, H, W)
+    want, clamped = m64.l1_normalize(x6, 3), m64.l1_clamped(x6, 3)
+    q = {}
+    for g in range(G):
+        q[f"y{g}"] = _close(f"y{g}", r.outputs[g], want[:, g], 1e-5, 1e-6, rel_only=clamped[:, g])
+        mc.check([mc.Cmp(f"y{g} zero set", r.outputs[g], x6[:, g] == 0, "zeros")])
+    if r.grad_in is not None:
+        gys = np.stack([np.zeros_like(r.outputs[g]) if r.grad_out[g] is None else r.grad_out[g] for g in range(G)], 1)
+        q["gx"] = _close("gx", r.grad_in[0].reshape(x6.shape), m64.l1_normalize_adjoint(x6, gys, 3), 1e-4, 1e-5, rel_only=clamped)
+    return q
+
+
+def check_norm_regression(r, oracle=None):
+    x = r.args[0]
+    q = {"out": _close("out", r.outputs[0], m64.norm_regression(x)[0], 1e-5, 1e-4, px=x.shape[1])}
+    if r.grad_in is not None:
+        q["gx"] = _close("gx", r.grad_in[0], m64.norm_regression_adjoint(x, r.grad_out[0]), 1e-4, 1e-4, rel_only=m64.l1_clamped(x, 1))
+    return q
+
+
+def check_softmin(r, oracle=None):
+    """the backward is a function of the OUTPUT: the float64 adjoint at the y the call itself returned, as in misc_cases"""
+    x = r.args[0]
+    q = {"y": _close("y", r.outputs[0], m64.softmin(x), 2e-6, 1e-7)}
+    if r.grad_in is not None:
+        q["gx"] = _close("gx", r.grad_in[0], m64.softmin_adjoint(r.outputs[0], r.grad_out[0]), 1e-5, 1e-5)
+    return q
+
+
+def check_softmin_regression(r, oracle=None):
+    x = r.args[0]
+    q = {"out": _close("out", r.outputs[0], m64.softmin_regression(x), 1e-5, 1e-4, px=x.shape[1])}
+    if r.grad_in is not None:
+        q["gx"] = _close("gx", r.grad_in[0], m64.softmin_regression_adjoint(x, r.grad_out[0]), 1e-4, 1e-4)
+    return q
+
+
+def check_trilinear(r, oracle=None):
+    """misc_ref64 has no float64 statement on purpose: the reference is ATen on the CPU in fp32 (misc_cases._aten_trilinear)"""
+    x, size = r.args
+    gy = r.grad_out[0] if r.grad_out is not None else np.zeros(x.shape[:2] + tuple(size), np.float32)
+    wy, wgx = mc._aten_trilinear(x, gy, size)
+    q = {"y": _close("y", r.outputs[0], wy, 1e-5, 1e-6)}
+    if r.grad_in is not None:
+        q["gx"] = _close("gx", r.grad_in[0], wgx, 1e-5, 1e-5)
+    return q
+
+
+def check_lga_regress(r, oracle=None):
+    """One LGA pass y = LGA(x, f), then out = sum_d d y_d / max(sum_d |y_d|, eps).  Bars composed of the two ops' own:
+      out       misc_cases' bar of the normalised regression (rtol 1e-5, atol' in disparity units) on the float64 pass, PLUS what
+                the pass's own roundings do to it: to first order sum_d |d - out sgn(y_d)| / s * E_y, E_y = FACTOR x chain_bound
+                (y is signed -- filters are -- so sum_d d y_d cancels, and E_y / s is not small against 1e-5)
+      backward  gy = the float64 adjoint of the regression, held by ITS bar (rtol 1e-4, atol' as everywhere); the LGA pass
+                behind it gets FACTOR x chain_bound for its own roundings plus that allowance on gy pushed through |f| (gx)
+                and through |taps of x| (gf), both by lga_backward on absolute values."""
+    x, f, radius, ndisp = r.args
+    go = r.grad_out[0] if r.grad_in is not None else np.zeros(x.shape[:1] + x.shape[2:], np.float32)
+    y = lga_ref64.lga_forward(x, f, radius)
+    gy = m64.norm_regression_adjoint(y, go)
+    R = lga_ref64.chain_bound(x, f, gy, radius, 1)
+    out, s = m64.norm_regression(y)
+    D = x.shape[1]
+    d = np.arange(D, dtype=np.float64).reshape(1, D, 1, 1)
+    through = (np.abs(d - out[:, None] * np.sign(y)) * FACTOR * R["y"]).sum(1) / s
+    q = {"out": _within("out", r.outputs[0], out, 1e-5 * np.abs(out) + _atol_px(1e-4, D) + through)}
+    if r.grad_in is not None:
+        e_gy = 1e-4 * np.abs(gy) + _atol(1e-4, gy)
+        extra = lga_ref64.lga_backward(np.abs(x), np.abs(f), e_gy, radius)
+        for k, i in (("gx", 0), ("gf", 1)):
+            q[k] = _within(k, r.grad_in[i], R["want"][k], FACTOR * R[k] + extra[i])
+    return q
+
+
+def _relu_adjoint(r, y, scale, i_t, i_rem):
+    """g = grad_y where the call's own y > 0; rem takes g (the same bits), t takes scale[c] * g: one rounding of an exact product"""
+    gy = r.grad_out[0]
+    g = np.where(y > 0, gy, np.float32(0))
+    q = {}
+    if i_rem is not None and r.grad_in[i_rem] is not None:
+        mc.check([mc.Cmp("g_rem", r.grad_in[i_rem], g, "bits")])
+        q["g_rem"] = 0.0
+    if r.grad_in[i_t] is not None:
+        C = g.shape[1]
+        want = g if scale is None else (g.astype(np.float64) * scale.astype(np.float64).reshape((1, C) + (1,) * (g.ndim - 2))).astype(np.float32)
+        mc.check([mc.Cmp("g_t", r.grad_in[i_t], want, "equal")])
+        q["g_t"] = 0.0
+    return q
+
+
+def _affine_relu(name, got, t, rem, scale, shift, relu=True):
+    """y = relu(scale[c] t + shift[c] + rem) in at most three fp32 roundings (product, two additions; an fma build has two),
+    each at most u times a partial result that |scale t| + |shift| + |rem| bounds: the case tables' EQUAL on dyadic inputs
+    becomes 3 u (|scale t| + |shift| + |rem|) on real ones, one rounding where there is nothing but t + rem.  The ReLU is
+    1-Lipschitz: the bar holds through it, and where float64 is above / below the bar the sign is decided."""
+    C = t.shape[1]
+    b = lambda v: v.astype(np.float64).reshape((1, C) + (1,) * (t.ndim - 2))      # noqa: E731
+    t64 = t.astype(np.float64)
+    rem64 = 0.0 if rem is None else rem.astype(np.float64)
+    if scale is None:
+        s, bar = t64 + rem64, ONE_ROUNDING * np.abs(t64 + rem64)
+    else:
+        s = b(scale) * t64 + b(shift) + rem64
+        bar = 3 * ONE_ROUNDING * (np.abs(b(scale) * t64) + np.abs(b(shift)) + np.abs(rem64))
+    if relu:
+        assert not (got[s < -bar] != 0).any() and not (got[s > bar] <= 0).any(), (name, "zero set")
+    return _within(name, got, np.maximum(s, 0.0) if relu else s, bar)
+
+
+def check_residual_relu(r, oracle=None):
+    t, rem, scale, shift, _ = r.args
+    q = {"y": _affine_relu("y", r.outputs[0], t, rem, scale, shift)}
+    if r.grad_in is not None:
+        q.update(_relu_adjoint(r, r.outputs[0], scale, 0, 1))
+    return q
+
+
+def check_bn_apply(r, oracle=None):
+    x, rem, scale, shift, relu, _ = r.args
+    q = {"y": _affine_relu("y", r.outputs[0], x, rem, scale, shift, relu)}
+    if r.grad_in is not None:
+        y = r.outputs[0] if relu else np.ones_like(r.outputs[0])
+        q.update(_relu_adjoint(r, y, scale, 0, 1 if rem is not None else None))
+    return q
+
+
+def check_bn_relu(r, oracle=None):
+    """bn_cases.check on the recorded tensors: a Case built around them (nothing generated, nothing nudged).  Recorded data
+    cannot be nudged away from the ReLU's kink, so at the elements that float64 cannot decide for fp32 (|z| <= 4 B_y) the
+    mask is the call's own y > 0; everywhere else float64 decides (bn_ref64.Reference, relu_positive)."""
+    x, rem, weight, bias, rmean, rvar, momentum, eps, relu = r.args
+    N, C = x.shape[:2]
+    shape = (N, C, x.size // (N * C))
+    c = object.__new__(bn_cases.Case)
+    c.name, c.shape, c.relu, c.offset, c.exact, c.momentum, c.eps = repr(r), shape, bool(relu), 0, False, momentum, eps
+    c.x, c.rem = x.reshape(shape), None if rem is None else rem.reshape(shape)
+    c.compare_grads = r.grad_in is not None
+    c.gy = r.grad_out[0].reshape(shape) if c.compare_grads else np.zeros(shape, np.float32)
+    c.weight, c.bias, c.running_mean, c.running_var, c.nudged = weight, bias, rmean, rvar, 0
+    c.mean_term = True                               # model data: channels whose spread is far below their mean (bn_cases)
+    y = r.outputs[0].reshape(shape)
+    c._ref = bn_ref64.Reference(*c.inputs(), relu_positive=y > 0)
+    got = {"y": y, "running_mean": None, "running_var": None}
+    if rmean is not None:
+        # the op updates its running statistics in place: what the call left in them is what the NEXT reader found
+        got["running_mean"], got["running_var"] = r.after.get(4, rmean), r.after.get(5, rvar)
+    want = [False] * 4
+    if c.compare_grads:
+        for i, key in enumerate(("grad_x", "grad_rem", "grad_weight", "grad_bias")):
+            if r.grad_in[i] is not None:
+                got[key], want[i] = (r.grad_in[i].reshape(shape) if i < 2 else r.grad_in[i]), True
+    q = bn_cases.check(c, got, want=tuple(want), verbose=False, saved=False)
+    q["undecided"] = float(c.ref.undecided().sum())
+    return q
+
+
+def check_disparity_loss(r, oracle=None):
+    target, params, _, kinds, mask_mode, *preds = r.args
+    p = dict(zip(loss_ref64.PARAMS, (float(v) for v in params)))
+    P = len(preds)
+    gl = float(r.grad_out[0]) if r.grad_out is not None else 1.0
+    want = tuple(g is not None for g in r.grad_in[5:5 + P]) if r.grad_in is not None else (False,) * P
+    c = loss_cases.Case(repr(r), target.shape, preds, target, tuple(kinds), [p["w0"], p["w1"], p["w2"]][:P], thresh=p["thresh"],
+                        alpha=p["alpha"], mask_mode=int(mask_mode), grad_loss=gl, want=want, hi=p["hi"], lo=p["lo"], rate=p["rate"])
+    loss_cases.check_forward(c, r.outputs[0], r.outputs[1], verbose=False)
+    if r.grad_in is not None:
+        loss_cases.check_grads(c, list(r.grad_in[5:5 + P]))
+    return {"loss": abs(float(r.outputs[0]) - c.ref.loss) / (loss_cases.SUM_RTOL * abs(c.ref.loss) + loss_cases.TINY)}
+
+
+def check_myloss2(r, oracle=None):
+    """MyLoss2Function is pure tensor arithmetic (kept for API parity): loss_ref64's stage-by-stage statement, every element
+    valid, loss_cases' relative bars (sums 2^-18, gradients 2^-20 against float64)"""
+    a, b = r.args[:2]
+    thresh, alpha = (r.args[2] if len(r.args) > 2 else 1), (r.args[3] if len(r.args) > 3 else 2)      # the Function's defaults
+    c = loss_cases.Case(repr(r), (1, 1, a.size), [a], b, (1,), (1.0,), thresh=thresh, alpha=alpha, hi=np.inf,
+                        grad_loss=float(r.grad_out[0]) if r.grad_out is not None else 1.0)
+    assert c.ref.count == a.size
+    assert loss_cases.close(r.outputs[0], c.ref.loss, loss_cases.SUM_RTOL), (float(r.outputs[0]), c.ref.loss)
+    q = {"loss": abs(float(r.outputs[0]) - c.ref.loss) / (loss_cases.SUM_RTOL * abs(c.ref.loss) + loss_cases.TINY)}
+    if r.grad_in is not None:
+        g64 = c.ref.grads(c.grad_loss, np.float64)[0].reshape(a.shape)
+        q["grad"] = _within("grad", r.grad_in[0], g64, loss_cases.GRAD_RTOL * np.abs(g64) + loss_cases.TINY)
+    return q
+
+
+CHECKERS = {
+    "SgaFunction": check_sga, "OracleSga": check_sga, "_sga_infer": check_sga_infer, "sga_forward_infer": check_sga_infer,
+    "OracleLgaChain": check_lga, **{k: check_lga for k in LGA_PASSES},
+    "GetCostVolumeFunction": check_cost_volume, "DisparityRegressionFunction": check_disparity_regression,
+    "L1NormalizeGroupsFunction": check_l1_normalize, "NormDisparityRegressionFunction": check_norm_regression,
+    "SoftminFunction": check_softmin, "SoftminDisparityRegressionFunction": check_softmin_regression,
+    "TrilinearUpsampleFunction": check_trilinear, "LgaRegressFunction": check_lga_regress,
+    "ResidualReluFunction": check_residual_relu, "BnApplyFunction": check_bn_apply, "BnReluFunction": check_bn_relu,
+    "DisparityLossFunction": check_disparity_loss, "MyLoss2Function": check_myloss2,
+}
+
+
+def check_all(records, oracle, kinds=None, report=None):
+    """every record through the checker of its kind (kinds: only these -- the CPU calibration).  A recorded kind without a
+    checker fails here, by name.  -> {(kind, key): largest error / bound over the records of that kind}; report: a list that
+    gets one line per record"""
+    missing = sorted({r.kind for r in records if r.kind not in CHECKERS})
+    assert not missing, f"recorded op calls without a checker: {missing}"
+    worst = collections.OrderedDict()
+    for i, r in enumerate(records):
+        if kinds is not None and r.kind not in kinds:
+            continue
+        q = CHECKERS[r.kind](r, oracle)
+        for k, v in q.items():
+            worst[(r.kind, k)] = max(worst.get((r.kind, k), 0.0), v)
+        if report is not None:
+            report.append(f"{i:3d} {r!r}: " + " ".join(f"{k}={v:.3g}" for k, v in q.items()))
+    return worst
+
+
+def kinds_of(records):
+    return collections.Counter(r.kind for r in records)
+
+
+def fmt(worst):
+    return "\n".join(f"  {kind:36s} {key:12s} {v:.3f}" for (kind, key), v in worst.items())
