@@ -11,7 +11,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libganet_hip.so"
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -65,6 +65,11 @@ _PROTOS = {
     "ganet_bn_train_forward": [_P] * 10 + [_I] * 6 + [_P],
     "ganet_bn_train_backward": [_P] * 12 + [_I] * 4 + [_P],
     "ganet_bn_apply_forward": [_P] * 5 + [_I] * 4 + [_P],
+    "ganet_stereo_input_workspace": [_I] * 3,
+    "ganet_stereo_input_stats": [_P] * 3 + [_I] * 3 + [_P],
+    "ganet_stereo_input_apply": [_P] * 5 + [_I] * 9 + [_P],
+    "ganet_window_f32": [_P] * 2 + [_I] * 8 + [_P],
+    "ganet_disparity_to_u16": [_P] * 2 + [_I] * 7 + [_P],
     "ganet_selftest_dpp": [_P, _P, _P],
     "ganet_selftest_dpp_wave": [_P, _P, _P],
 }

@@ -3,6 +3,7 @@
 // Compiled by hipcc for gfx950 (product) and by g++ -DGA_HIPSIM (CPU test emulator).
 #include "ga_common.h"
 #include "bn_kernels.h"
+#include "io_kernels.h"
 #include "lga_kernels.h"
 #include "loss_kernels.h"
 #include "misc_kernels.h"
@@ -1637,6 +1638,115 @@ GA_EXPORT int ganet_bn_apply_forward(const float *x, const float *rem, const flo
   if (vec) GA_LAUNCH((bn_affine_apply<4>), grid, dim3(BN_BLOCK), st, x, rem, scale, shift, y, g, relu);
   else GA_LAUNCH((bn_affine_apply<1>), grid, dim3(BN_BLOCK), st, x, rem, scale, shift, y, g, relu);
   return check_launch("batch norm apply");
+}
+
+// ---- image front and back end (predict.py:75-114, :132-138; dataloader/dataset.py:48-92) --------------------------------------
+namespace {
+int io_rows(i64 pixels)
+{
+  const i64 want = (pixels + IO_PIX_PER_BLOCK - 1) / IO_PIX_PER_BLOCK;
+  return (int)(want < IO_MAX_ROWS ? want : IO_MAX_ROWS);
+}
+
+int io_blocks(i64 units)
+{
+  const i64 want = (units + IO_BLOCK - 1) / IO_BLOCK;
+  return (int)(want < 1 ? 1 : (want < IO_MAX_BLOCKS ? want : IO_MAX_BLOCKS));
+}
+
+int io_check_image(const char *who, int H, int W, int CP)
+{
+  if (H <= 0 || W <= 0) return fail(GANET_E_INVALID, "%s: non-positive size H=%d W=%d", who, H, W);
+  if (CP != 3 && CP != 4) return fail(GANET_E_INVALID, "%s: CP=%d bytes per pixel, 3 or 4", who, CP);
+  if ((i64)H * W > (1 << 24))
+    return fail(GANET_E_INVALID, "%s: %lld pixels; the integer sums are exact up to 2^24", who, (long long)H * W);
+  return GANET_OK;
+}
+
+int io_check_window(const char *who, int Hc, int Wc, int oy, int ox)
+{
+  if (Hc <= 0 || Wc <= 0) return fail(GANET_E_INVALID, "%s: non-positive window Hc=%d Wc=%d", who, Hc, Wc);
+  if ((i64)Hc * Wc > (1 << 28)) return fail(GANET_E_INVALID, "%s: window of %lld pixels", who, (long long)Hc * Wc);
+  const int lim = 1 << 28;
+  if (oy < -lim || oy > lim || ox < -lim || ox > lim) return fail(GANET_E_INVALID, "%s: offset (%d, %d) out of range", who, oy, ox);
+  return GANET_OK;
+}
+}  // namespace
+
+GA_EXPORT int ganet_stereo_input_workspace(int H, int W, int CP)
+{
+  GA_TRY(io_check_image("ganet_stereo_input_workspace", H, W, CP));
+  return 2 * IO_MAX_ROWS * IO_ROW;
+}
+
+GA_EXPORT int ganet_stereo_input_stats(const uint8_t *left, const uint8_t *right, uint64_t *workspace, int H, int W, int CP,
+                                       void *stream)
+{
+  const char *who = "ganet_stereo_input_stats";
+  if (!left || !right || !workspace) return fail(GANET_E_INVALID, "%s: null pointer", who);
+  GA_TRY(io_check_image(who, H, W, CP));
+  IoImage g = {left, right, H, W, CP, io_rows((i64)H * W), (aligned16(left) ? 1 : 0) | (aligned16(right) ? 2 : 0)};
+  GA_LAUNCH(io_stats, dim3(g.R, 2), dim3(IO_BLOCK), (hipStream_t)stream, g, (u64 *)workspace);
+  return check_launch("stereo input statistics");
+}
+
+GA_EXPORT int ganet_stereo_input_apply(const uint8_t *left, const uint8_t *right, const uint64_t *workspace, float *left_out,
+                                       float *right_out, int H, int W, int CP, int Hc, int Wc, int oy, int ox_left, int ox_right,
+                                       int form, void *stream)
+{
+  const char *who = "ganet_stereo_input_apply";
+  if (!left || !right || !workspace || !left_out || !right_out) return fail(GANET_E_INVALID, "%s: null pointer", who);
+  GA_TRY(io_check_image(who, H, W, CP));
+  GA_TRY(io_check_window(who, Hc, Wc, oy, ox_left));
+  GA_TRY(io_check_window(who, Hc, Wc, oy, ox_right));
+  if (form != 0 && form != 1) return fail(GANET_E_INVALID, "%s: form=%d (0: table, 1: direct)", who, form);
+  IoImage g = {left, right, H, W, CP, io_rows((i64)H * W), 0};
+  IoWindow w = {left_out, right_out, Hc, Wc, oy, ox_left, ox_right};
+  const bool vec = Wc % 4 == 0 && aligned16(left_out) && aligned16(right_out);
+  const dim3 grid(io_blocks((i64)Hc * (vec ? Wc / 4 : Wc)), 2);
+  hipStream_t st = (hipStream_t)stream;
+  const u64 *ws = (const u64 *)workspace;
+  if (vec && form == 0) GA_LAUNCH((io_apply<4, true>), grid, dim3(IO_BLOCK), st, g, w, ws);
+  else if (vec) GA_LAUNCH((io_apply<4, false>), grid, dim3(IO_BLOCK), st, g, w, ws);
+  else if (form == 0) GA_LAUNCH((io_apply<1, true>), grid, dim3(IO_BLOCK), st, g, w, ws);
+  else GA_LAUNCH((io_apply<1, false>), grid, dim3(IO_BLOCK), st, g, w, ws);
+  return check_launch("stereo input apply");
+}
+
+GA_EXPORT int ganet_window_f32(const float *src, float *dst, int H, int W, int Hc, int Wc, int oy, int ox, int sub_bits,
+                               int fill_bits, void *stream)
+{
+  const char *who = "ganet_window_f32";
+  if (!src || !dst) return fail(GANET_E_INVALID, "%s: null pointer", who);
+  if (src == dst) return fail(GANET_E_INVALID, "%s: dst must not alias src", who);
+  if (H <= 0 || W <= 0 || (i64)H * W > (1 << 28)) return fail(GANET_E_INVALID, "%s: bad size H=%d W=%d", who, H, W);
+  GA_TRY(io_check_window(who, Hc, Wc, oy, ox));
+  const float sub = bn_float(sub_bits), fill = bn_float(fill_bits);
+  const bool vec = Wc % 4 == 0 && aligned16(dst);
+  const dim3 grid(io_blocks((i64)Hc * (vec ? Wc / 4 : Wc)));
+  hipStream_t st = (hipStream_t)stream;
+  if (vec) GA_LAUNCH((io_window_f32<4>), grid, dim3(IO_BLOCK), st, src, dst, H, W, Hc, Wc, oy, ox, sub, fill);
+  else GA_LAUNCH((io_window_f32<1>), grid, dim3(IO_BLOCK), st, src, dst, H, W, Hc, Wc, oy, ox, sub, fill);
+  return check_launch("float window");
+}
+
+GA_EXPORT int ganet_disparity_to_u16(const float *disp, uint16_t *out, int Hd, int Wd, int h, int w, int oy, int ox,
+                                     int scale_bits, void *stream)
+{
+  const char *who = "ganet_disparity_to_u16";
+  if (!disp || !out) return fail(GANET_E_INVALID, "%s: null pointer", who);
+  if (Hd <= 0 || Wd <= 0 || h <= 0 || w <= 0 || (i64)Hd * Wd > (1 << 28))
+    return fail(GANET_E_INVALID, "%s: bad size Hd=%d Wd=%d h=%d w=%d", who, Hd, Wd, h, w);
+  if (oy < 0 || ox < 0 || (i64)oy + h > Hd || (i64)ox + w > Wd)
+    return fail(GANET_E_INVALID, "%s: the [%d, %d] window at (%d, %d) leaves the [%d, %d] map", who, h, w, oy, ox, Hd, Wd);
+  const float scale = bn_float(scale_bits);
+  const bool vec = aligned16(out);
+  const i64 n = (i64)h * w;
+  const dim3 grid(io_blocks(vec ? n / 8 : n));
+  hipStream_t st = (hipStream_t)stream;
+  if (vec) GA_LAUNCH((io_disp_u16<8>), grid, dim3(IO_BLOCK), st, disp, out, Wd, h, w, oy, ox, scale);
+  else GA_LAUNCH((io_disp_u16<1>), grid, dim3(IO_BLOCK), st, disp, out, Wd, h, w, oy, ox, scale);
+  return check_launch("disparity to 16 bit");
 }
 
 GA_EXPORT int ganet_selftest_dpp_wave(int *scratch_dev, int *host_out, void *stream)

@@ -18,7 +18,8 @@ from .GANet import _check, _p, _sga_infer, _stream
 
 __all__ = ["L1NormalizeGroupsFunction", "NormDisparityRegressionFunction", "normalize_guidance", "normalize_filters",
            "sga_forward_infer", "SoftminFunction", "SoftminDisparityRegressionFunction", "TrilinearUpsampleFunction", "LgaRegressFunction",
-           "ResidualReluFunction", "DisparityLossFunction", "disparity_loss_workspace", "BnReluFunction", "BnApplyFunction"]
+           "ResidualReluFunction", "DisparityLossFunction", "disparity_loss_workspace", "BnReluFunction", "BnApplyFunction",
+           "stereo_input", "window_f32", "disparity_to_u16"]
 
 
 def _lib():
@@ -483,3 +484,69 @@ class BnApplyFunction(Function):
                 g_rem, gx = g, g * scale.view((1, C) + (1,) * (g.dim() - 2))
         return (gx if ctx.needs_input_grad[0] else None, g_rem if ctx.has_rem and ctx.needs_input_grad[1] else None,
                 None, None, None, None)
+
+
+# ---- image front and back end: plain functions, integers in, nothing differentiable out -----------------------------------------
+
+def _check_io(t, dtype, dims, what):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{what}: ganet_amd ops need HIP (cuda) tensors: there is no CPU path")
+    if t.dtype != dtype:
+        raise TypeError(f"{what}: expected {dtype}, got {t.dtype}")
+    if t.dim() != dims or not t.is_contiguous():
+        raise ValueError(f"{what}: expected a contiguous {dims}-d tensor, got {tuple(t.shape)}")
+
+
+def stereo_input(left_u8, right_u8, crop_hw, oy, ox_left, ox_right, out_left=None, out_right=None, form=0):
+    """The model's input from a stereo pair of uint8 images [H, W, 3 | 4] (ganet_stereo_input_stats / _apply; predict.py:92-114,
+    :75-90, dataloader/dataset.py:64-92): every channel standardised with its own mean and std, then
+    out[c, y, x] = pixel (y + oy, x + ox_left) of the left image, resp. (y + oy, x + ox_right) of the right one, 0 outside.
+    Returns (left, right), fp32 [3, Hc, Wc] each -- out_left / out_right where given (contiguous, e.g. batch[i] of a
+    [B, 3, Hc, Wc] tensor).  A constant channel gives 0 (the reference: NaN).  Two launches; the integer workspace is a fresh
+    8 KB from the caching allocator: no state, no host synchronisation, any stream, capturable.  form=1: the direct form of
+    the apply pass instead of the table (the same bits; for measurement)."""
+    _check_io(left_u8, torch.uint8, 3, "left image")
+    _check_io(right_u8, torch.uint8, 3, "right image")
+    if left_u8.shape != right_u8.shape or left_u8.device != right_u8.device:
+        raise ValueError(f"the two images must have one shape and device, got {tuple(left_u8.shape)} and {tuple(right_u8.shape)}")
+    H, W, CP = left_u8.shape
+    Hc, Wc = (int(v) for v in crop_hw)
+    with torch.cuda.device_of(left_u8):
+        outs = []
+        for t in (out_left, out_right):
+            if t is None:
+                t = torch.empty((3, Hc, Wc), dtype=torch.float32, device=left_u8.device)
+            _check_io(t, torch.float32, 3, "output")
+            if tuple(t.shape) != (3, Hc, Wc) or t.device != left_u8.device:
+                raise ValueError(f"output: expected [3, {Hc}, {Wc}] on the images' device, got {tuple(t.shape)}")
+            outs.append(t)
+        lib = _lib()
+        ws = torch.empty(lib.query("ganet_stereo_input_workspace", H, W, CP), dtype=torch.int64, device=left_u8.device)
+        lib.call("ganet_stereo_input_stats", _p(left_u8), _p(right_u8), _p(ws), H, W, CP, _stream())
+        lib.call("ganet_stereo_input_apply", _p(left_u8), _p(right_u8), _p(ws), _p(outs[0]), _p(outs[1]), H, W, CP, Hc, Wc,
+                 int(oy), int(ox_left), int(ox_right), int(form), _stream())
+    return outs[0], outs[1]
+
+
+def window_f32(src, crop_hw, oy, ox, sub=0.0, fill=0.0):
+    """dst[Hc, Wc] = src[y + oy, x + ox] - sub inside the fp32 map src [H, W], `fill` outside (ganet_window_f32;
+    dataloader/dataset.py:53-74: the training target)."""
+    _check_io(src, torch.float32, 2, "map")
+    Hc, Wc = (int(v) for v in crop_hw)
+    with torch.cuda.device_of(src):
+        dst = torch.empty((Hc, Wc), dtype=torch.float32, device=src.device)
+        _lib().call("ganet_window_f32", _p(src), _p(dst), src.shape[0], src.shape[1], Hc, Wc, int(oy), int(ox), _float_bits(sub),
+                    _float_bits(fill), _stream())
+    return dst
+
+
+def disparity_to_u16(disp, hw, oy=0, ox=0, scale=256.0):
+    """torch.uint16 [h, w] = sat(trunc(disp[y + oy, x + ox] * scale)) from the fp32 map disp [Hd, Wd] (ganet_disparity_to_u16;
+    predict.py:134-138).  Below 0 and NaN give 0, 65536 and above 65535 (the reference's astype wraps there)."""
+    _check_io(disp, torch.float32, 2, "disparity map")
+    h, w = (int(v) for v in hw)
+    with torch.cuda.device_of(disp):
+        out = torch.empty((h, w), dtype=torch.uint16, device=disp.device)
+        _lib().call("ganet_disparity_to_u16", _p(disp), _p(out), disp.shape[0], disp.shape[1], h, w, int(oy), int(ox),
+                    _float_bits(scale), _stream())
+    return out

@@ -5,11 +5,13 @@ from torch.nn.modules.module import Module
 
 from ..functions.fused import (BnApplyFunction, BnReluFunction, DisparityLossFunction, LgaRegressFunction, NormDisparityRegressionFunction, ResidualReluFunction,
                                SoftminDisparityRegressionFunction, SoftminFunction, TrilinearUpsampleFunction,
-                               disparity_loss_workspace, normalize_filters, normalize_guidance, sga_forward_infer)
+                               disparity_loss_workspace, disparity_to_u16, normalize_filters, normalize_guidance, sga_forward_infer,
+                               stereo_input, window_f32)
 from ..functions.GANet import Lga2Function, LgaFunction, SgaFunction
 
 __all__ = ["GuidedSGA", "GuidedSGABnRelu", "NormalizedLGA2", "NormDisparityRegression", "SoftminDisparityRegression",
-           "DispAggTail", "TrilinearUpsample", "ResidualBnRelu", "DisparityLoss", "folded_bn", "BnRelu", "bn_relu_path"]
+           "DispAggTail", "TrilinearUpsample", "ResidualBnRelu", "DisparityLoss", "folded_bn", "BnRelu", "bn_relu_path",
+           "StereoInput", "DisparityOutput", "predict_offsets"]
 
 
 def folded_bn(bn, refresh=False):
@@ -280,3 +282,64 @@ class DisparityLoss(Module):
         if need not in self._workspace:
             self._workspace[need] = disparity_loss_workspace(target, *target.shape)
         return DisparityLossFunction.apply(target, self._params[dev], self._workspace[need], self.kinds, self.mask_mode, *outputs)
+
+
+def predict_offsets(h, w, crop_height, crop_width):
+    """(oy, ox) of predict.py:75-90 for an [h, w] image: output pixel (y, x) is image pixel (y + oy, x + ox).  An image no
+    larger than the crop sits in the bottom-right corner (oy = h - Hc, ox = w - Wc, both <= 0); one larger BOTH ways is
+    centre-cropped with int((w - Wc) / 2).  Larger one way only: the reference takes its crop branch with a negative start,
+    which slices from the far end and returns an array of another shape; here it is a ValueError."""
+    if h <= crop_height and w <= crop_width:
+        return h - crop_height, w - crop_width
+    if h > crop_height and w > crop_width:
+        return int((h - crop_height) / 2), int((w - crop_width) / 2)
+    raise ValueError(f"a {h}x{w} image is larger than the {crop_height}x{crop_width} crop one way and not the other: "
+                     "the reference's test_transform has no answer for it")
+
+
+class StereoInput(Module):
+    """The front end of predict.py as one op: forward(left_u8, right_u8) == test_transform(load_data(..)) (predict.py:92-114,
+    :75-90) for two uint8 images [H, W, 3 | 4] ON THE DEVICE: every channel standardised, padded to the bottom-right or
+    centre-cropped to [crop_height, crop_width].  Returns (left, right, (h, w)), fp32 [1, 3, Hc, Wc] each.
+    A constant channel gives 0 where the reference has NaN (its std is 0).  Two launches, no host synchronisation,
+    capturable, any stream; uint8 tensors on a HIP device only."""
+
+    def __init__(self, crop_height, crop_width):
+        super().__init__()
+        self.crop_height, self.crop_width = int(crop_height), int(crop_width)
+
+    def forward(self, left_u8, right_u8):
+        h, w = left_u8.shape[:2]
+        oy, ox = predict_offsets(h, w, self.crop_height, self.crop_width)
+        left, right = self.window(left_u8, right_u8, oy, ox, ox)
+        return left[None], right[None], (h, w)
+
+    def window(self, left_u8, right_u8, oy, ox_left, ox_right, out_left=None, out_right=None):
+        """The same with explicit offsets: the training crop of dataloader/dataset.py:64-92 (oy = start_y - pad_y,
+        ox_right = start_x - pad_x, ox_left = ox_right + shift_x).  Returns fp32 [3, Hc, Wc] each, written to out_left /
+        out_right where given (slices of batch tensors)."""
+        return stereo_input(left_u8, right_u8, (self.crop_height, self.crop_width), oy, ox_left, ox_right, out_left, out_right)
+
+    def target_window(self, disp, oy, ox, sub=0.0, fill=1000.0):
+        """The training target under the same crop (dataset.py:53-74): disp [H, W] fp32 -> [Hc, Wc], `fill` outside the
+        map, `sub` subtracted inside (the reference lowers the whole crop by shift_x: sub = shift_x, fill = 1000 - shift_x)."""
+        return window_f32(disp, (self.crop_height, self.crop_width), oy, ox, sub, fill)
+
+
+class DisparityOutput(Module):
+    """The back end of predict.py:132-138: forward(disp [1, Hc, Wc] or [Hc, Wc] fp32, (h, w)) -> torch.uint16 [h, w], the
+    padding of StereoInput taken off again (a cropped image keeps the whole map), values scaled by 256 and truncated.
+    Values below 0 and NaN give 0, 65536 and above 65535; the reference's astype('uint16') wraps there."""
+
+    def __init__(self, scale=256.0):
+        super().__init__()
+        self.scale = float(scale)
+
+    def forward(self, disp, hw):
+        if disp.dim() == 3 and disp.shape[0] == 1:
+            disp = disp[0]
+        Hc, Wc = disp.shape
+        h, w = hw
+        if h <= Hc and w <= Wc:
+            return disparity_to_u16(disp.contiguous(), (h, w), Hc - h, Wc - w, self.scale)
+        return disparity_to_u16(disp.contiguous(), (Hc, Wc), 0, 0, self.scale)

@@ -113,6 +113,14 @@ def predict(model, left, right):
     return model(left, right)
 
 
+def predict_images(model, left_u8, right_u8, crop_hw):
+    """predict.py:92-138 from two uint8 images [H, W, 3 | 4] on the device to the uint16 [h, w] disparity image it saves:
+    StereoInput -> predict -> DisparityOutput, no numpy on the pixel path."""
+    from ganet_amd.modules.fused import DisparityOutput, StereoInput
+    left, right, hw = StereoInput(*crop_hw)(left_u8, right_u8)
+    return DisparityOutput()(predict(model, left, right), hw)
+
+
 def synthetic_batch(batch, height, width, max_disp, device, seed=123):
     """Standardised random images and a plausible disparity map (no dataset offline): same shapes and value ranges as
     dataloader/dataset.py produces (per-channel zero-mean unit-variance images, disparities in [0, max_disp))."""

@@ -35,7 +35,7 @@ extern "C" {
 #define GANET_E_UNSUPPORTED (-2)  /* shape outside the compiled kernel set         */
 #define GANET_E_RUNTIME (-3)      /* HIP runtime / launch error                    */
 
-#define GANET_ABI_VERSION 13      /* v13 = v12 + ganet_bn_workspace / _train_forward / _train_backward / _apply_forward (BatchNorm + ReLU) */
+#define GANET_ABI_VERSION 14      /* v14 = v13 + ganet_stereo_input_workspace / _stats / _apply, ganet_window_f32, ganet_disparity_to_u16 (image front and back end) */
 int ganet_abi_version(void);
 const char *ganet_last_error(void);
 /* 1 if this build runs the lockstep CPU emulator (tests only), 0 for the gfx950 build */
@@ -343,6 +343,53 @@ int ganet_bn_train_backward(const float *x, const float *rem, const float *grad_
                             int N, int C, int S, int relu, void *stream);
 int ganet_bn_apply_forward(const float *x, const float *rem, const float *scale, const float *shift, float *y,
                            int N, int C, int S, int relu, void *stream);
+
+/* ---------------------------------------------------------------- image I/O ------ */
+
+/* ABI v14.  The two ends around the model: a stereo pair of uint8 images becomes the model's standardised fp32 input, the
+ * disparity map becomes the 16-bit image the reference saves (ganet_amd/csrc/io_kernels.h; tests/io_ref64.py states the
+ * arithmetic in Python integers and float64).
+ *
+ * Images: uint8 [H, W, CP], interleaved, CP = 3 | 4; the first three bytes of a pixel are its channels.  N = H W <= 2^24.
+ *   statistics   per image and channel S1 = sum v, S2 = sum v^2 in 64-bit integers (exact, order-independent: two runs are
+ *                bit-identical), one workspace row per block, plain stores, no atomics
+ *   apply        mean = double(S1) / double(N), std = sqrt(double(N S2 - S1 S1) / (double(N) double(N))), the numerator in
+ *                64-bit integers; out = float32((double(v) - mean) / std), every fp64 operation rounded on its own.
+ *                DEVIATION: a constant channel (N S2 == S1 S1) gives 0 everywhere; the reference divides by zero and
+ *                returns NaN (Inf for nothing: v - mean is 0 there).
+ *                left_out / right_out: fp32 [3, Hc, Wc] each (two pointers: they may be slices of batch tensors);
+ *                out[c, y, x] = channel c of pixel (y + oy, x + ox_left) of the left image, resp. (y + oy, x + ox_right) of
+ *                the right one, 0 where that pixel lies outside the image.  No byte outside the images is read.
+ *                form: 0 the 3 x 256 table of results built once per block (a channel has only 256), 1 the same expression per
+ *                element (same bits; kept for measurement).
+ * workspace: ganet_stereo_input_workspace(H, W, CP) 8-byte words, private to the pair of calls until both have run.
+ * _stats takes 16-byte requests from an image whose base is 16-byte aligned and single bytes from any other address; _apply
+ * stores 16 bytes where Wc % 4 == 0 and both outputs are 16-byte aligned.
+ * CP other than 3 | 4, H W > 2^24, a NULL pointer, non-positive sizes: GANET_E_INVALID.
+ * Replaces: predict.py:92-114 (load_data: `(r - np.mean(r)) / np.std(r)` per channel, float64 temporaries, float32 result) and
+ *           :75-90 (test_transform: oy = H - Hc, ox = W - Wc pads to the bottom-right, int((W - Wc) / 2) centre-crops);
+ *           dataloader/dataset.py:64-92 (train_transform: the random crop, the left image shifted by shift_x). */
+int ganet_stereo_input_workspace(int H, int W, int CP);
+int ganet_stereo_input_stats(const uint8_t *left, const uint8_t *right, uint64_t *workspace,
+                             int H, int W, int CP, void *stream);
+int ganet_stereo_input_apply(const uint8_t *left, const uint8_t *right, const uint64_t *workspace,
+                             float *left_out, float *right_out, int H, int W, int CP, int Hc, int Wc,
+                             int oy, int ox_left, int ox_right, int form, void *stream);
+
+/* dst[Hc, Wc] = inside ? src[y + oy, x + ox] - sub : fill on fp32 maps, src [H, W]; sub_bits / fill_bits: the two fp32 values
+ * as their bit patterns.  dst must not alias src.
+ * Replaces: dataloader/dataset.py:53-74 (train_transform: the target padded with 1000, cropped, `target - shift_x`) and
+ *           :100-104 (test_transform's padded target). */
+int ganet_window_f32(const float *src, float *dst, int H, int W, int Hc, int Wc, int oy, int ox,
+                     int sub_bits, int fill_bits, void *stream);
+
+/* out[h, w] (uint16, contiguous) = sat(trunc(disp[y + oy, x + ox] * scale)), disp fp32 [Hd, Wd]; the window must lie inside
+ * the map.  The product is one fp32 multiplication, truncation is toward zero.
+ * DEVIATION: values below 0 and NaN give 0, values >= 65536 and +Inf give 65535; the reference's astype('uint16') wraps or is
+ * undefined there.  16-byte stores where `out` is 16-byte aligned.
+ * Replaces: predict.py:132-138 (un-pad with oy = Hd - h, ox = Wd - w, `(temp * 256).astype('uint16')`). */
+int ganet_disparity_to_u16(const float *disp, uint16_t *out, int Hd, int Wd, int h, int w, int oy, int ox,
+                           int scale_bits, void *stream);
 
 /* ---------------------------------------------------------------- diagnostics ---- */
 
