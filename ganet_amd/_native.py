@@ -56,6 +56,8 @@ _PROTOS = {
     "ganet_softmin_regression_backward": [_P] * 6 + [_I] * 4 + [_P],
     "ganet_trilinear_upsample_forward": [_P] * 2 + [_I] * 7 + [_P],
     "ganet_trilinear_upsample_backward": [_P] * 2 + [_I] * 7 + [_P],
+    "ganet_up_softmin_regression_forward": [_P] * 4 + [_I] * 7 + [_P],
+    "ganet_up_softmin_regression_backward": [_P] * 7 + [_I] * 7 + [_P],
     "ganet_residual_relu_forward": [_P] * 5 + [_I] * 5 + [_P],
     "ganet_residual_relu_backward": [_P] * 5 + [_I] * 5 + [_P],
     "ganet_disparity_loss_workspace": [_I] * 3,

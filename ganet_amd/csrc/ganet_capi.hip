@@ -7,6 +7,7 @@
 #include "lga_kernels.h"
 #include "loss_kernels.h"
 #include "misc_kernels.h"
+#include "disp_tail_kernels.h"
 #include "sga_kernels.h"
 #include "sga_row_kernels.h"
 #include "sga_col_kernels.h"
@@ -1404,6 +1405,46 @@ GA_EXPORT int ganet_softmin_regression_backward(const float *x, const float *out
   GA_LAUNCH(softmin_regression_bwd, dim3(ew_grid((i64)N * HW)), dim3(256), (hipStream_t)stream, x, out, mx, ssum,
             grad_out, grad_x, N, Dn, HW);
   return check_launch("softmin regression backward");
+}
+
+// ---- Disp.forward behind conv32x1 without the up-sampled volume (models/GANet_deep.py:214-219; disp_tail_kernels.h) ----
+namespace {
+int check_up_tail(const char *who, int N, int Di, int Hi, int Wi, int Do, int Ho, int Wo)
+{
+  if (N <= 0 || Di <= 0 || Hi <= 0 || Wi <= 0 || Do <= 0 || Ho <= 0 || Wo <= 0)
+    return fail(GANET_E_INVALID, "%s: non-positive size", who);
+  if (Do >= (1 << 24)) return fail(GANET_E_INVALID, "%s: Do=%d, the disparity index must be exact in float (Do < 2^24)", who, Do);
+  return GANET_OK;
+}
+}  // namespace
+
+// models/GANet_deep.py:214-219
+GA_EXPORT int ganet_up_softmin_regression_forward(const float *x, float *out, float *mx, float *ssum, int N, int Di, int Hi,
+                                                  int Wi, int Do, int Ho, int Wo, void *stream)
+{
+  if (!x || !out || !mx || !ssum) return fail(GANET_E_INVALID, "ganet_up_softmin_regression_forward: null pointer");
+  GA_TRY(check_up_tail("ganet_up_softmin_regression_forward", N, Di, Hi, Wi, Do, Ho, Wo));
+  GA_LAUNCH(up_softmin_regression_fwd, dim3(ew_grid((i64)N * Ho * Wo)), dim3(256), (hipStream_t)stream, x, out, mx, ssum,
+            (i64)N, up_axis(Di, Do), up_axis(Hi, Ho), up_axis(Wi, Wo));
+  return check_launch("up-sampled softmin regression forward");
+}
+
+// models/GANet_deep.py:214-219 (adjoint): the column pass into gcol_ws [N,Di,Ho,Wo], then the H x W gather of
+// trilinear_up_bwd on N*Di slices of depth 1 -> 1
+GA_EXPORT int ganet_up_softmin_regression_backward(const float *x, const float *out, const float *mx, const float *ssum,
+                                                   const float *grad_out, float *gcol_ws, float *grad_x, int N, int Di,
+                                                   int Hi, int Wi, int Do, int Ho, int Wo, void *stream)
+{
+  if (!x || !out || !mx || !ssum || !grad_out || !gcol_ws || !grad_x)
+    return fail(GANET_E_INVALID, "ganet_up_softmin_regression_backward: null pointer");
+  GA_TRY(check_up_tail("ganet_up_softmin_regression_backward", N, Di, Hi, Wi, Do, Ho, Wo));
+  GA_LAUNCH(up_softmin_regression_bwd_cols, dim3(ew_grid((i64)N * Ho * Wo)), dim3(256), (hipStream_t)stream, x, out, mx, ssum,
+            grad_out, gcol_ws, (i64)N, up_axis(Di, Do), up_axis(Hi, Ho), up_axis(Wi, Wo));
+  GA_TRY(check_launch("up-sampled softmin regression backward (columns)"));
+  const i64 S = (i64)N * Di;
+  GA_LAUNCH(trilinear_up_bwd, dim3(ew_grid(S * Hi * Wi)), dim3(256), (hipStream_t)stream, (const float *)gcol_ws, grad_x, S,
+            up_axis(1, 1), up_axis(Hi, Ho), up_axis(Wi, Wo));
+  return check_launch("up-sampled softmin regression backward (gather)");
 }
 
 // ---- SGABlock's residual epilogue (models/GANet_deep.py:270-277) --------------------

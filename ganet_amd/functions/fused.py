@@ -17,7 +17,8 @@ from .. import _native
 from .GANet import _check, _p, _sga_infer, _stream
 
 __all__ = ["L1NormalizeGroupsFunction", "NormDisparityRegressionFunction", "normalize_guidance", "normalize_filters",
-           "sga_forward_infer", "SoftminFunction", "SoftminDisparityRegressionFunction", "TrilinearUpsampleFunction", "LgaRegressFunction",
+           "sga_forward_infer", "SoftminFunction", "SoftminDisparityRegressionFunction", "TrilinearUpsampleFunction",
+           "UpSoftminRegressionFunction", "LgaRegressFunction",
            "ResidualReluFunction", "DisparityLossFunction", "disparity_loss_workspace", "BnReluFunction", "BnApplyFunction",
            "stereo_input", "window_f32", "disparity_to_u16"]
 
@@ -207,6 +208,43 @@ class TrilinearUpsampleFunction(Function):
         with torch.cuda.device_of(g):
             gx = torch.empty((N, C, Di, Hi, Wi), dtype=g.dtype, device=g.device)
             _lib().call("ganet_trilinear_upsample_backward", _p(g), _p(gx), N * C, Di, Hi, Wi, Do, Ho, Wo, _stream())
+        return gx, None
+
+
+class UpSoftminRegressionFunction(Function):
+    """out[N,Ho,Wo] = sum_d d * softmin_d(F.interpolate(x, size, mode='trilinear', align_corners=False)): Disp.forward behind
+    its conv32x1 (models/GANet_deep.py:214-219) without the up-sampled volume.  x is [N,1,Di,Hi,Wi] (the convolution's
+    output) or [N,Di,Hi,Wi]; size = (Do, Ho, Wo).  Saved: x and three [N,Ho,Wo] maps.  The backward takes its column
+    workspace [N,Di,Ho,Wo] from the caching allocator: no state, no host synchronisation, any stream, capturable."""
+
+    @staticmethod
+    def forward(ctx, x, size):
+        _check(x)
+        if x.dim() == 5 and x.shape[1] != 1:
+            raise ValueError(f"expected [N,1,Di,Hi,Wi] or [N,Di,Hi,Wi], got {tuple(x.shape)}")
+        if x.dim() not in (4, 5) or len(size) != 3:
+            raise ValueError("UpSoftminRegression expects [N,1,Di,Hi,Wi] or [N,Di,Hi,Wi] and a 3-element output size")
+        N, (Di, Hi, Wi) = x.shape[0], x.shape[-3:]
+        Do, Ho, Wo = (int(v) for v in size)
+        ctx.dims = (N, Di, Hi, Wi, Do, Ho, Wo)
+        with torch.cuda.device_of(x):
+            out = torch.empty((N, Ho, Wo), dtype=x.dtype, device=x.device)
+            mx, ssum = torch.empty_like(out), torch.empty_like(out)
+            _lib().call("ganet_up_softmin_regression_forward", _p(x), _p(out), _p(mx), _p(ssum), *ctx.dims, _stream())
+        ctx.save_for_backward(x, out, mx, ssum)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, out, mx, ssum = ctx.saved_tensors
+        g = grad_out.contiguous()
+        _check(g)
+        N, Di, Hi, Wi, Do, Ho, Wo = ctx.dims
+        with torch.cuda.device_of(g):
+            ws = torch.empty((N, Di, Ho, Wo), dtype=x.dtype, device=x.device)
+            gx = torch.empty_like(x)
+            _lib().call("ganet_up_softmin_regression_backward", _p(x), _p(out), _p(mx), _p(ssum), _p(g), _p(ws), _p(gx),
+                        *ctx.dims, _stream())
         return gx, None
 
 

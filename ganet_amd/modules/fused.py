@@ -4,13 +4,13 @@ import torch
 from torch.nn.modules.module import Module
 
 from ..functions.fused import (BnApplyFunction, BnReluFunction, DisparityLossFunction, LgaRegressFunction, NormDisparityRegressionFunction, ResidualReluFunction,
-                               SoftminDisparityRegressionFunction, SoftminFunction, TrilinearUpsampleFunction,
+                               SoftminDisparityRegressionFunction, SoftminFunction, TrilinearUpsampleFunction, UpSoftminRegressionFunction,
                                disparity_loss_workspace, disparity_to_u16, normalize_filters, normalize_guidance, sga_forward_infer,
                                stereo_input, window_f32)
 from ..functions.GANet import Lga2Function, LgaFunction, SgaFunction
 
 __all__ = ["GuidedSGA", "GuidedSGABnRelu", "NormalizedLGA2", "NormDisparityRegression", "SoftminDisparityRegression",
-           "DispAggTail", "TrilinearUpsample", "ResidualBnRelu", "DisparityLoss", "folded_bn", "BnRelu", "bn_relu_path",
+           "DispAggTail", "TrilinearUpsample", "DispTail", "ResidualBnRelu", "DisparityLoss", "folded_bn", "BnRelu", "bn_relu_path",
            "StereoInput", "DisparityOutput", "predict_offsets"]
 
 
@@ -225,6 +225,23 @@ class TrilinearUpsample(Module):
 
     def forward(self, x, size):
         return TrilinearUpsampleFunction.apply(x.contiguous(), tuple(int(v) for v in size))
+
+
+class DispTail(Module):
+    """Disp.forward behind its conv32x1 (models/GANet_deep.py:214-219) as ONE op: forward(c), c = the convolution's output
+    [N,1,D,H,W] (or [N,D,H,W]) -> the disparity map [N, zoom*H, zoom*W] =
+    DisparityRegression(Softmin(dim=1)(F.interpolate(c, [maxdisp+1, zoom*H, zoom*W], mode='trilinear'))).  The up-sampled
+    volume exists in neither direction (TrilinearUpsample -> SoftminDisparityRegression writes, saves, re-reads and mirrors
+    it with a gradient volume); the backward's workspace is a third of it at zoom 3."""
+
+    def __init__(self, maxdisp, zoom=3):
+        super().__init__()
+        self.ndisp = maxdisp + 1
+        self.zoom = zoom
+
+    def forward(self, c):
+        H, W = c.shape[-2:]
+        return UpSoftminRegressionFunction.apply(c.contiguous(), (self.ndisp, self.zoom * H, self.zoom * W))
 
 
 class DisparityLoss(Module):

@@ -13,12 +13,15 @@ use_fused_bn (opt-in on top, or alone):
   BasicConv.forward models/GANet_deep.py:35-41     conv -> bn -> F.relu(inplace=True): BatchNorm (batch statistics in training
                                                    mode, folded in eval mode) and ReLU -> BnRelu; the convolution stays MIOpen's
   SGABlock's tail   models/GANet_deep.py:270-277   where use_fused_ops has put a ResidualBnRelu: -> BnRelu(bn)(t, rem)
+use_fused_disp_tail (opt-in on top, or alone):
+  Disp.forward      models/GANet_deep.py:214-219   everything behind conv32x1 -- up-sampling, Softmin, regression -> DispTail: the
+                                                   up-sampled volume is never written, forward or backward
 """
 import types
 
 import torch
 
-from ganet_amd.modules.fused import (BnRelu, DispAggTail, GuidedSGA, GuidedSGABnRelu, ResidualBnRelu, SoftminDisparityRegression,
+from ganet_amd.modules.fused import (BnRelu, DispAggTail, DispTail, GuidedSGA, GuidedSGABnRelu, ResidualBnRelu, SoftminDisparityRegression,
                                      TrilinearUpsample)
 
 _UP = TrilinearUpsample()
@@ -88,5 +91,23 @@ def use_fused_bn(model):
             n += 1
         elif kind == "SGABlock" and isinstance(m.__dict__.get("_fused_tail"), ResidualBnRelu):
             object.__setattr__(m, "_fused_tail", BnRelu(m._fused_tail.bn, relu=True))      # the same call form (t, rem)
+            n += 1
+    return n
+
+
+def _disp_tail_forward(self, x):
+    return self._fused_tail(self.conv32x1(x))
+
+
+def use_fused_disp_tail(model):
+    """Every Disp (the two auxiliary disparities of training) on DispTail.  Alone, or after use_fused_ops, whose
+    TrilinearUpsample -> SoftminDisparityRegression pair it replaces; DispAgg is not touched.  Returns the number of call
+    sites rebound."""
+    n = 0
+    for m in model.modules():
+        if type(m).__name__ == "Disp":
+            # (object.__setattr__: the helper stays out of the module tree, state_dict keys do not move)
+            object.__setattr__(m, "_fused_tail", DispTail(m.maxdisp))
+            m.forward = types.MethodType(_disp_tail_forward, m)
             n += 1
     return n

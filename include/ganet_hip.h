@@ -35,7 +35,7 @@ extern "C" {
 #define GANET_E_UNSUPPORTED (-2)  /* shape outside the compiled kernel set         */
 #define GANET_E_RUNTIME (-3)      /* HIP runtime / launch error                    */
 
-#define GANET_ABI_VERSION 14      /* v14 = v13 + ganet_stereo_input_workspace / _stats / _apply, ganet_window_f32, ganet_disparity_to_u16 (image front and back end) */
+#define GANET_ABI_VERSION 14      /* v14 = v13 + ganet_stereo_input_workspace / _stats / _apply, ganet_window_f32, ganet_disparity_to_u16 (image front and back end); v14 also holds ganet_up_softmin_regression_forward / _backward (additions only: every earlier entry is unchanged) */
 int ganet_abi_version(void);
 const char *ganet_last_error(void);
 /* 1 if this build runs the lockstep CPU emulator (tests only), 0 for the gfx950 build */
@@ -267,6 +267,19 @@ int ganet_trilinear_upsample_forward(const float *x, float *y, int S, int Di, in
                                      int Do, int Ho, int Wo, void *stream);
 int ganet_trilinear_upsample_backward(const float *grad_y, float *grad_x, int S, int Di, int Hi, int Wi,
                                       int Do, int Ho, int Wo, void *stream);
+
+/* Disp.forward behind its conv32x1 (models/GANet_deep.py:214-219) in one pass, without the up-sampled volume:
+ *   v = F.interpolate(x [N,Di,Hi,Wi], size=[Do,Ho,Wo], mode='trilinear', align_corners=False),  out [N,Ho,Wo] = sum_od od *
+ *   softmin_od(v).  Per axis the source index and weight are those of ganet_trilinear_upsample_forward (PyTorch's rule
+ *   evaluated in float32), the association is ATen's (W, then H, then D).  mx, ssum [N,Ho,Wo] are kept for the backward,
+ *   which recomputes v and the probabilities from x: it writes the depth-reduced gradient columns to gcol_ws [N,Di,Ho,Wo]
+ *   (every element is written; the caller provides the memory, contents irrelevant) and gathers grad_x [N,Di,Hi,Wi] from
+ *   them: deterministic, no atomics.  Any sizes (down-sampling included); Do < 2^24. */
+int ganet_up_softmin_regression_forward(const float *x, float *out, float *mx, float *ssum,
+                                        int N, int Di, int Hi, int Wi, int Do, int Ho, int Wo, void *stream);
+int ganet_up_softmin_regression_backward(const float *x, const float *out, const float *mx, const float *ssum,
+                                         const float *grad_out, float *gcol_ws /* [N,Di,Ho,Wo] */, float *grad_x,
+                                         int N, int Di, int Hi, int Wi, int Do, int Ho, int Wo, void *stream);
 
 /* The end of SGABlock.forward (models/GANet_deep.py:270-277): behind `conv_refine` (Conv3d + BatchNorm3d, no ReLU) the
  * block adds its input back and applies ReLU,  `x += rem; return relu(x)`.  One pass:
