@@ -58,6 +58,10 @@ _PROTOS = {
     "ganet_trilinear_upsample_backward": [_P] * 2 + [_I] * 7 + [_P],
     "ganet_up_softmin_regression_forward": [_P] * 4 + [_I] * 7 + [_P],
     "ganet_up_softmin_regression_backward": [_P] * 7 + [_I] * 7 + [_P],
+    "ganet_disp_conv_workspace": [_I] * 5,
+    "ganet_disp_conv_forward": [_P] * 3 + [_I] * 5 + [_P],
+    "ganet_disp_conv_backward_data": [_P] * 3 + [_I] * 5 + [_P],
+    "ganet_disp_conv_backward_weight": [_P] * 4 + [_I] * 5 + [_P],
     "ganet_residual_relu_forward": [_P] * 5 + [_I] * 5 + [_P],
     "ganet_residual_relu_backward": [_P] * 5 + [_I] * 5 + [_P],
     "ganet_disparity_loss_workspace": [_I] * 3,

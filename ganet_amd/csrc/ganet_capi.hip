@@ -8,6 +8,7 @@
 #include "loss_kernels.h"
 #include "misc_kernels.h"
 #include "disp_tail_kernels.h"
+#include "disp_conv_kernels.h"
 #include "sga_kernels.h"
 #include "sga_row_kernels.h"
 #include "sga_col_kernels.h"
@@ -1445,6 +1446,94 @@ GA_EXPORT int ganet_up_softmin_regression_backward(const float *x, const float *
   GA_LAUNCH(trilinear_up_bwd, dim3(ew_grid(S * Hi * Wi)), dim3(256), (hipStream_t)stream, (const float *)gcol_ws, grad_x, S,
             up_axis(1, 1), up_axis(Hi, Ho), up_axis(Wi, Wo));
   return check_launch("up-sampled softmin regression backward (gather)");
+}
+
+// ---- the tails' conv32x1: Conv3d(C, 1, 3, 1, 1, bias=False) (models/GANet_deep.py:212, 232; disp_conv_kernels.h) ----
+namespace {
+int check_disp_conv(const char *who, int N, int C, int D, int H, int W, DispConvGeom &g, dim3 &grid)
+{
+  if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0)
+    return fail(GANET_E_INVALID, "%s: non-positive size N=%d C=%d D=%d H=%d W=%d", who, N, C, D, H, W);
+  if (C > DCV_MAX_C) return fail(GANET_E_UNSUPPORTED, "%s: C=%d, at most %d channels", who, C, DCV_MAX_C);
+  g.N = N; g.C = C; g.D = D; g.H = H; g.W = W;
+  g.W4 = (W + DCV_PX - 1) / DCV_PX;
+  g.groups = (i64)H * g.W4;
+  const i64 bx = (g.groups + 63) / 64, by = ((i64)D + DCV_DEPTH - 1) / DCV_DEPTH;
+  if (bx > 0x7fffffff || by > 65535 || N > 65535)
+    return fail(GANET_E_UNSUPPORTED, "%s: N=%d D=%d H=%d W=%d is beyond the launch grid", who, N, D, H, W);
+  grid = dim3((unsigned)bx, (unsigned)by, (unsigned)N);
+  return GANET_OK;
+}
+i64 disp_conv_rows(const dim3 &grid) { return (i64)grid.x * grid.y * grid.z; }
+}  // namespace
+
+GA_EXPORT int ganet_disp_conv_workspace(int N, int C, int D, int H, int W)
+{
+  DispConvGeom g;
+  dim3 grid;
+  GA_TRY(check_disp_conv("ganet_disp_conv_workspace", N, C, D, H, W, g, grid));
+  const i64 n = disp_conv_rows(grid) * 27 * C;
+  if (n > 0x7fffffff) return fail(GANET_E_UNSUPPORTED, "ganet_disp_conv_workspace: %lld elements do not fit the answer", n);
+  return (int)n;
+}
+
+GA_EXPORT int ganet_disp_conv_forward(const float *x, const float *weight, float *y, int N, int C, int D, int H, int W,
+                                      void *stream)
+{
+  if (!x || !weight || !y) return fail(GANET_E_INVALID, "ganet_disp_conv_forward: null pointer");
+  DispConvGeom g;
+  dim3 grid;
+  GA_TRY(check_disp_conv("ganet_disp_conv_forward", N, C, D, H, W, g, grid));
+  if (y == x || y == weight) return fail(GANET_E_INVALID, "ganet_disp_conv_forward: y must not alias an input");
+  const dim3 block(64 * DCV_WAVES);
+  if (W % 4 == 0 && aligned16(x) && aligned16(y))
+    GA_LAUNCH((disp_conv_fwd<true>), grid, block, (hipStream_t)stream, x, weight, y, g);
+  else
+    GA_LAUNCH((disp_conv_fwd<false>), grid, block, (hipStream_t)stream, x, weight, y, g);
+  return check_launch("disp conv forward");
+}
+
+GA_EXPORT int ganet_disp_conv_backward_data(const float *grad_y, const float *weight, float *grad_x, int N, int C, int D,
+                                            int H, int W, void *stream)
+{
+  if (!grad_y || !weight || !grad_x) return fail(GANET_E_INVALID, "ganet_disp_conv_backward_data: null pointer");
+  DispConvGeom g;
+  dim3 grid;
+  GA_TRY(check_disp_conv("ganet_disp_conv_backward_data", N, C, D, H, W, g, grid));
+  if (grad_x == grad_y || grad_x == weight)
+    return fail(GANET_E_INVALID, "ganet_disp_conv_backward_data: grad_x must not alias an input");
+  const dim3 block(64 * DCV_WAVES);
+  if (W % 4 == 0 && aligned16(grad_y) && aligned16(grad_x))
+    GA_LAUNCH((disp_conv_bwd_data<true>), grid, block, (hipStream_t)stream, grad_y, weight, grad_x, g);
+  else
+    GA_LAUNCH((disp_conv_bwd_data<false>), grid, block, (hipStream_t)stream, grad_y, weight, grad_x, g);
+  return check_launch("disp conv backward (data)");
+}
+
+GA_EXPORT int ganet_disp_conv_backward_weight(const float *x, const float *grad_y, float *workspace, float *grad_weight,
+                                              int N, int C, int D, int H, int W, void *stream)
+{
+  if (!x || !grad_y || !workspace || !grad_weight)
+    return fail(GANET_E_INVALID, "ganet_disp_conv_backward_weight: null pointer");
+  DispConvGeom g;
+  dim3 grid;
+  GA_TRY(check_disp_conv("ganet_disp_conv_backward_weight", N, C, D, H, W, g, grid));
+  if (grad_weight == x || grad_weight == grad_y || workspace == x || workspace == grad_y || workspace == grad_weight)
+    return fail(GANET_E_INVALID, "ganet_disp_conv_backward_weight: workspace and grad_weight must not alias anything");
+  const i64 rows = disp_conv_rows(grid);
+  if (rows * 27 * C > 0x7fffffff)
+    return fail(GANET_E_UNSUPPORTED, "ganet_disp_conv_backward_weight: the workspace is beyond ganet_disp_conv_workspace's answer");
+  const dim3 block(64 * DCV_WAVES);
+  hipStream_t st = (hipStream_t)stream;
+  if (W % 4 == 0 && aligned16(x) && aligned16(grad_y))
+    GA_LAUNCH((disp_conv_bwd_weight_partials<true>), grid, block, st, x, grad_y, workspace, g);
+  else
+    GA_LAUNCH((disp_conv_bwd_weight_partials<false>), grid, block, st, x, grad_y, workspace, g);
+  GA_TRY(check_launch("disp conv backward (weight partials)"));
+  const int K = 27 * C;
+  GA_LAUNCH(disp_conv_bwd_weight_sum, dim3((unsigned)((K + DCV_SUM_COLS - 1) / DCV_SUM_COLS)),
+            dim3(DCV_SUM_COLS * DCV_SUM_SLICES), st, (const float *)workspace, grad_weight, K, rows);
+  return check_launch("disp conv backward (weight sum)");
 }
 
 // ---- SGABlock's residual epilogue (models/GANet_deep.py:270-277) --------------------

@@ -18,7 +18,7 @@ from .GANet import _check, _p, _sga_infer, _stream
 
 __all__ = ["L1NormalizeGroupsFunction", "NormDisparityRegressionFunction", "normalize_guidance", "normalize_filters",
            "sga_forward_infer", "SoftminFunction", "SoftminDisparityRegressionFunction", "TrilinearUpsampleFunction",
-           "UpSoftminRegressionFunction", "LgaRegressFunction",
+           "UpSoftminRegressionFunction", "DispConvFunction", "disp_conv_grad_input", "disp_conv_grad_weight", "LgaRegressFunction",
            "ResidualReluFunction", "DisparityLossFunction", "disparity_loss_workspace", "BnReluFunction", "BnApplyFunction",
            "stereo_input", "window_f32", "disparity_to_u16"]
 
@@ -246,6 +246,70 @@ class UpSoftminRegressionFunction(Function):
             _lib().call("ganet_up_softmin_regression_backward", _p(x), _p(out), _p(mx), _p(ssum), _p(g), _p(ws), _p(gx),
                         *ctx.dims, _stream())
         return gx, None
+
+
+_CONV_BWD = ([1, 1, 1], [1, 1, 1], [1, 1, 1], False, [0, 0, 0], 1)     # stride, padding, dilation, transposed, output_padding, groups
+
+
+def disp_conv_grad_input(grad_y, weight, x, native=True):
+    """grad_x [N,C,D,H,W] of DispConvFunction from grad_y [N,1,D,H,W] (contiguous): ganet_disp_conv_backward_data, or ATen's
+    data gradient of the same convolution (native=False).  Plain function, nothing is recorded for autograd."""
+    if not native:
+        return torch.ops.aten.convolution_backward(grad_y, x, weight, None, *_CONV_BWD, [True, False, False])[0]
+    _check(grad_y, weight)
+    with torch.cuda.device_of(grad_y):
+        gx = torch.empty(x.shape, dtype=grad_y.dtype, device=grad_y.device)
+        _lib().call("ganet_disp_conv_backward_data", _p(grad_y), _p(weight), _p(gx), *x.shape, _stream())
+    return gx
+
+
+def disp_conv_grad_weight(x, grad_y, weight, native=True):
+    """grad_weight [1,C,3,3,3] of DispConvFunction: ganet_disp_conv_backward_weight (two launches, no atomics: two runs give the
+    same bits; the workspace is a fresh tensor from the caching allocator), or ATen's weight gradient (native=False)."""
+    if not native:
+        return torch.ops.aten.convolution_backward(grad_y, x, weight, None, *_CONV_BWD, [False, True, False])[1]
+    _check(x, grad_y)
+    with torch.cuda.device_of(x):
+        ws = torch.empty(_lib().query("ganet_disp_conv_workspace", *x.shape), dtype=x.dtype, device=x.device)
+        gw = torch.empty(weight.shape, dtype=x.dtype, device=x.device)
+        _lib().call("ganet_disp_conv_backward_weight", _p(x), _p(grad_y), _p(ws), _p(gw), *x.shape, _stream())
+    return gw
+
+
+class DispConvFunction(Function):
+    """y [N,1,D,H,W] = F.conv3d(x [N,C,D,H,W], weight [1,C,3,3,3], stride 1, padding 1): the tails' conv32x1
+    (models/GANet_deep.py:212, 232) on the streaming kernels of disp_conv_kernels.h instead of MIOpen's one-column GEMM.
+    Saved: x and weight, nothing else; neither is written.  Only the gradients autograd asks for are computed
+    (disp_conv_grad_input, disp_conv_grad_weight): no state, no host synchronisation, any stream, capturable.
+    `directions`: which of "forward", "data", "weight" run here; the others go to ATen."""
+
+    ALL = ("forward", "data", "weight")
+
+    @staticmethod
+    def forward(ctx, x, weight, directions=ALL):
+        _check(x, weight)
+        if x.dim() != 5 or weight.dim() != 5 or tuple(weight.shape) != (1, x.shape[1], 3, 3, 3):
+            raise ValueError(f"expected x [N,C,D,H,W] and weight [1,C,3,3,3], got {tuple(x.shape)} and {tuple(weight.shape)}")
+        N, C, D, H, W = x.shape
+        ctx.directions = tuple(directions)
+        with torch.cuda.device_of(x):
+            if "forward" in ctx.directions:
+                y = torch.empty((N, 1, D, H, W), dtype=x.dtype, device=x.device)
+                _lib().call("ganet_disp_conv_forward", _p(x), _p(weight), _p(y), N, C, D, H, W, _stream())
+            else:
+                y = torch.nn.functional.conv3d(x, weight, None, 1, 1)
+        ctx.save_for_backward(x, weight)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_y):
+        x, weight = ctx.saved_tensors
+        g = grad_y.contiguous()
+        _check(g)
+        gx = disp_conv_grad_input(g, weight, x, "data" in ctx.directions) if ctx.needs_input_grad[0] else None
+        gw = disp_conv_grad_weight(x, g, weight, "weight" in ctx.directions) if ctx.needs_input_grad[1] else None
+        return gx, gw, None
 
 
 class LgaRegressFunction(Function):

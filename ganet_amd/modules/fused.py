@@ -3,14 +3,14 @@ reference-compatible modules in ganet_amd.modules.GANet are unchanged."""
 import torch
 from torch.nn.modules.module import Module
 
-from ..functions.fused import (BnApplyFunction, BnReluFunction, DisparityLossFunction, LgaRegressFunction, NormDisparityRegressionFunction, ResidualReluFunction,
+from ..functions.fused import (BnApplyFunction, BnReluFunction, DisparityLossFunction, DispConvFunction, LgaRegressFunction, NormDisparityRegressionFunction, ResidualReluFunction,
                                SoftminDisparityRegressionFunction, SoftminFunction, TrilinearUpsampleFunction, UpSoftminRegressionFunction,
                                disparity_loss_workspace, disparity_to_u16, normalize_filters, normalize_guidance, sga_forward_infer,
                                stereo_input, window_f32)
 from ..functions.GANet import Lga2Function, LgaFunction, SgaFunction
 
 __all__ = ["GuidedSGA", "GuidedSGABnRelu", "NormalizedLGA2", "NormDisparityRegression", "SoftminDisparityRegression",
-           "DispAggTail", "TrilinearUpsample", "DispTail", "ResidualBnRelu", "DisparityLoss", "folded_bn", "BnRelu", "bn_relu_path",
+           "DispAggTail", "TrilinearUpsample", "DispTail", "DispConv", "ResidualBnRelu", "DisparityLoss", "folded_bn", "BnRelu", "bn_relu_path",
            "StereoInput", "DisparityOutput", "predict_offsets"]
 
 
@@ -242,6 +242,33 @@ class DispTail(Module):
     def forward(self, c):
         H, W = c.shape[-2:]
         return UpSoftminRegressionFunction.apply(c.contiguous(), (self.ndisp, self.zoom * H, self.zoom * W))
+
+
+class DispConv(Module):
+    """The tails' conv32x1 (models/GANet_deep.py:212, 232) on our own kernels: DispConv(conv)(x) == conv(x) for
+    conv = nn.Conv3d(C, 1, (3,3,3), (1,1,1), (1,1,1), bias=False), C <= 64.  The module holds the convolution it was given and
+    reads conv.weight at every call: the parameter object, its state_dict key and whatever the optimizer holds do not move.
+    `directions`: which of "forward", "data" (gradient of the input), "weight" (gradient of the weight) run on the HIP kernels;
+    the others stay on ATen."""
+
+    def __init__(self, conv, directions=DispConvFunction.ALL):
+        super().__init__()
+        if not isinstance(conv, torch.nn.Conv3d):
+            raise TypeError("DispConv wraps an nn.Conv3d")
+        want = dict(out_channels=1, kernel_size=(3, 3, 3), stride=(1, 1, 1), padding=(1, 1, 1), dilation=(1, 1, 1), groups=1,
+                    padding_mode="zeros")
+        for k, v in want.items():
+            assert getattr(conv, k) == v, f"DispConv: the convolution has {k}={getattr(conv, k)}, expected {v}"
+        assert conv.bias is None, "DispConv: the convolution has a bias"
+        assert conv.in_channels <= 64, f"DispConv: {conv.in_channels} input channels, at most 64"
+        directions = tuple(directions)
+        if any(d not in DispConvFunction.ALL for d in directions):
+            raise ValueError(f"directions: a subset of {DispConvFunction.ALL}")
+        self.conv = conv                  # the caller's convolution (shared, not copied)
+        self.directions = directions
+
+    def forward(self, x):
+        return DispConvFunction.apply(x.contiguous(), self.conv.weight.contiguous(), self.directions)
 
 
 class DisparityLoss(Module):

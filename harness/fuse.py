@@ -16,12 +16,16 @@ use_fused_bn (opt-in on top, or alone):
 use_fused_disp_tail (opt-in on top, or alone):
   Disp.forward      models/GANet_deep.py:214-219   everything behind conv32x1 -- up-sampling, Softmin, regression -> DispTail: the
                                                    up-sampled volume is never written, forward or backward
+use_fused_disp_conv (opt-in, composes with all of the above in any order):
+  conv32x1          models/GANet_deep.py:212, 232  Conv3d(32, 1, 3, 1, 1) in Disp and DispAgg -> DispConv: streaming HIP kernels instead
+                                                   of MIOpen's one-column GEMM; the rebind is on the convolution INSTANCE, so whichever
+                                                   forward its owner has calls it
 """
 import types
 
 import torch
 
-from ganet_amd.modules.fused import (BnRelu, DispAggTail, DispTail, GuidedSGA, GuidedSGABnRelu, ResidualBnRelu, SoftminDisparityRegression,
+from ganet_amd.modules.fused import (BnRelu, DispAggTail, DispConv, DispTail, GuidedSGA, GuidedSGABnRelu, ResidualBnRelu, SoftminDisparityRegression,
                                      TrilinearUpsample)
 
 _UP = TrilinearUpsample()
@@ -109,5 +113,25 @@ def use_fused_disp_tail(model):
             # (object.__setattr__: the helper stays out of the module tree, state_dict keys do not move)
             object.__setattr__(m, "_fused_tail", DispTail(m.maxdisp))
             m.forward = types.MethodType(_disp_tail_forward, m)
+            n += 1
+    return n
+
+
+def _conv32x1_forward(self, x):
+    return self._fused_conv(x)
+
+
+def use_fused_disp_conv(model, directions=("forward", "data", "weight")):
+    """conv32x1 of every Disp and DispAgg on DispConv.  `forward` is rebound on the Conv3d instance itself: the stock forwards,
+    use_fused_ops' and use_fused_disp_tail's all call self.conv32x1(x), so it composes with them in any order.  The weight stays
+    the convolution's own parameter.  `directions`: which of "forward", "data", "weight" run on the HIP kernels (the rest stay
+    on ATen).  Returns the number of sites rebound: 3 on GANet_deep."""
+    n = 0
+    for m in model.modules():
+        if type(m).__name__ in ("Disp", "DispAgg") and isinstance(getattr(m, "conv32x1", None), torch.nn.Conv3d):
+            conv = m.conv32x1
+            # (object.__setattr__: the helper stays out of the module tree, state_dict keys do not move)
+            object.__setattr__(conv, "_fused_conv", DispConv(conv, directions))
+            conv.forward = types.MethodType(_conv32x1_forward, conv)
             n += 1
     return n

@@ -2,7 +2,7 @@
 """BASELINE.json configs[2]: full GANet-deep inference (9 GA layers... 7 SGA + 2 LGA2) on a KITTI-2015-sized pair
 (1248x384, max_disp 192) on one MI355X, the reference's model on this repository's ops.
 
-    python -m harness.infer [--model GANet_deep] [--height 384] [--width 1248] [--max_disp 192] [--fused] [--fused_bn] [--iters 5]
+    python -m harness.infer [--model GANet_deep] [--height 384] [--width 1248] [--max_disp 192] [--fused] [--fused_bn] [--fused_conv32] [--iters 5]
 
 Prints one JSON line: ms per forward pass (median of --iters, HIP events), peak device memory, parameter count.
 Random-init weights and synthetic standardised images (no checkpoint / dataset offline); predict.py:100-114 is the
@@ -35,6 +35,7 @@ def main():
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--fused", action="store_true", help="ganet_amd.modules.fused op chains instead of the stock call forms")
     ap.add_argument("--fused_bn", action="store_true", help="BatchNorm + ReLU behind every BasicConv on ganet_amd.modules.fused.BnRelu")
+    ap.add_argument("--fused_conv32", action="store_true", help="conv32x1 of every Disp / DispAgg on ganet_amd.modules.fused.DispConv (HIP kernels instead of MIOpen)")
     ap.add_argument("--no_miopen_find", dest="miopen_find", action="store_false",
                     help="MIOpen immediate mode (heuristic solver choice) instead of timing its solvers per shape")
     ap.add_argument("--kernel_share", action="store_true", help="add the per-group device-time table (torch.profiler over 2 extra passes)")
@@ -50,6 +51,7 @@ def main():
     model = steps.build_model(args.model, args.max_disp, dev)
     n_fused = fuse.use_fused_ops(model) if args.fused else 0
     n_fused_bn = fuse.use_fused_bn(model) if args.fused_bn else 0
+    n_fused_conv32 = fuse.use_fused_disp_conv(model) if args.fused_conv32 else 0
     left, right, _ = steps.synthetic_batch(args.batch, args.height, args.width, args.max_disp, dev)
     for _ in range(args.warmup):
         out = steps.predict(model, left, right)
@@ -74,6 +76,7 @@ def main():
         "input": [args.batch, 3, args.height, args.width], "max_disp": args.max_disp,
         "ops": "ganet_amd.modules.fused (%d call sites)" % n_fused if args.fused else "drop-in call forms (libs/)",
         "fused_bn": "BnRelu (%d call sites)" % n_fused_bn if args.fused_bn else False,
+        "fused_conv32": "DispConv (%d call sites)" % n_fused_conv32 if args.fused_conv32 else False,
         "ms_per_pair": round(times[len(times) // 2], 3), "ms_min": round(times[0], 3), "iters": args.iters,
         "peak_mem_GB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 3),
         "miopen_find": bool(args.miopen_find), "params": sum(p.numel() for p in model.parameters()), "dtype": "f32", "weights": "random init",

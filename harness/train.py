@@ -4,7 +4,7 @@ backward, DDP gradient all-reduce over RCCL, Adam -- at crop 240x624, max_disp 1
 8 GPUs), the reference's model on this repository's ops.
 
     python -m harness.train [--gpus N] [--model GANet_deep] [--crop_height 240] [--crop_width 624] [--max_disp 192]
-                            [--batch 1] [--steps 5] [--warmup 2] [--sync_bn] [--fused] [--fused_bn] [--fused_disp] [--resume CKPT] [--save CKPT]
+                            [--batch 1] [--steps 5] [--warmup 2] [--sync_bn] [--fused] [--fused_bn] [--fused_disp] [--fused_conv32] [--resume CKPT] [--save CKPT]
 
 N > 1: launched under torch.distributed.run (one rank per GPU) or, without a launcher, re-executes itself that way.
 Rank 0 prints one JSON line: ms per step (max over ranks), samples/s of the whole job, peak memory, loss values."""
@@ -47,6 +47,7 @@ def parse(argv=None):
     ap.add_argument("--fused", action="store_true")
     ap.add_argument("--fused_bn", action="store_true", help="BatchNorm + ReLU behind every BasicConv on ganet_amd.modules.fused.BnRelu")
     ap.add_argument("--fused_disp", action="store_true", help="every Disp behind its conv32x1 on ganet_amd.modules.fused.DispTail (no up-sampled volume)")
+    ap.add_argument("--fused_conv32", action="store_true", help="conv32x1 of every Disp / DispAgg on ganet_amd.modules.fused.DispConv (HIP kernels instead of MIOpen)")
     ap.add_argument("--kernel_share", action="store_true", help="add the per-group device-time table (torch.profiler over 2 extra steps, rank 0)")
     ap.add_argument("--resume", default="")
     ap.add_argument("--save", default="")
@@ -71,6 +72,7 @@ def run(args, hook=None):
         fuse.use_fused_ops(steps.unwrap(model))
     n_fused_bn = fuse.use_fused_bn(steps.unwrap(model)) if args.fused_bn else 0
     n_fused_disp = fuse.use_fused_disp_tail(steps.unwrap(model)) if args.fused_disp else 0
+    n_fused_conv32 = fuse.use_fused_disp_conv(steps.unwrap(model)) if args.fused_conv32 else 0
     opt = torch.optim.Adam(model.parameters(), lr=args.lr, betas=(0.9, 0.999))
     epoch0 = 0
     if args.resume:
@@ -111,6 +113,7 @@ def run(args, hook=None):
             "ops": "ganet_amd.modules.fused" if args.fused else "drop-in call forms (libs/)",
             "fused_bn": "BnRelu (%d call sites)" % n_fused_bn if args.fused_bn else False,
             "fused_disp": "DispTail (%d call sites)" % n_fused_disp if args.fused_disp else False,
+            "fused_conv32": "DispConv (%d call sites)" % n_fused_conv32 if args.fused_conv32 else False,
             "grad_allreduce": "DistributedDataParallel (RCCL)" if ctx.world_size > 1 and not cpu else
                               ("DistributedDataParallel (gloo)" if ctx.world_size > 1 else "none (1 rank)"),
             "peak_mem_GB": None if cpu else round(torch.cuda.max_memory_allocated() / 2 ** 30, 3),

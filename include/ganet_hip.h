@@ -35,7 +35,7 @@ extern "C" {
 #define GANET_E_UNSUPPORTED (-2)  /* shape outside the compiled kernel set         */
 #define GANET_E_RUNTIME (-3)      /* HIP runtime / launch error                    */
 
-#define GANET_ABI_VERSION 14      /* v14 = v13 + ganet_stereo_input_workspace / _stats / _apply, ganet_window_f32, ganet_disparity_to_u16 (image front and back end); v14 also holds ganet_up_softmin_regression_forward / _backward (additions only: every earlier entry is unchanged) */
+#define GANET_ABI_VERSION 14      /* v14 = v13 + ganet_stereo_input_workspace / _stats / _apply, ganet_window_f32, ganet_disparity_to_u16 (image front and back end); v14 also holds ganet_up_softmin_regression_forward / _backward and ganet_disp_conv_workspace / _forward / _backward_data / _backward_weight (additions only: every earlier entry is unchanged) */
 int ganet_abi_version(void);
 const char *ganet_last_error(void);
 /* 1 if this build runs the lockstep CPU emulator (tests only), 0 for the gfx950 build */
@@ -280,6 +280,28 @@ int ganet_up_softmin_regression_forward(const float *x, float *out, float *mx, f
 int ganet_up_softmin_regression_backward(const float *x, const float *out, const float *mx, const float *ssum,
                                          const float *grad_out, float *gcol_ws /* [N,Di,Ho,Wo] */, float *grad_x,
                                          int N, int Di, int Hi, int Wi, int Do, int Ho, int Wo, void *stream);
+
+/* The tails' conv32x1 = nn.Conv3d(C, 1, (3,3,3), (1,1,1), (1,1,1), bias=False) as streaming kernels (disp_conv_kernels.h): fp32,
+ * x [N,C,D,H,W], y and grad_y [N,1,D,H,W], weight and grad_weight [1,C,3,3,3] as ATen holds them, all contiguous; stride 1,
+ * padding 1, no dilation, no bias; [.] is zero outside the volume (predicated: nothing outside a tensor is read):
+ *   forward          y[n,d,h,w]               = sum_c sum_(kd,kh,kw) weight[c,kd,kh,kw] [x[n,c,d+kd-1,h+kh-1,w+kw-1]]
+ *   backward_data    grad_x[n,c,z,y,x]        = sum_(kd,kh,kw) weight[c,kd,kh,kw] [grad_y[n,z-kd+1,y-kh+1,x-kw+1]]
+ *   backward_weight  grad_weight[c,kd,kh,kw]  = sum_(n,d,h,w) grad_y[n,d,h,w] [x[n,c,d+kd-1,h+kh-1,w+kw-1]]
+ * backward_weight runs two launches: per-workgroup partial sums go to rows of `workspace` in a fixed order, a second launch
+ * adds the rows in index order in fp64 and rounds once.  No atomics anywhere: two runs give identical bits.
+ * workspace: ganet_disp_conv_workspace(N, C, D, H, W) floats, private to the call until it has run; contents irrelevant, every
+ * element of it and of every output is written exactly once.  Outputs must not alias inputs.  No host synchronisation,
+ * capturable.  16-byte requests where W % 4 == 0 and the volumes' bases are 16-byte aligned, 4-byte ones otherwise.
+ * 64-bit element offsets.  NULL pointer, non-positive size: GANET_E_INVALID.  C > 64, more than 65535 * 8 planes, N > 65535, a
+ * workspace of 2^31 elements or more: GANET_E_UNSUPPORTED.  A refused call launches nothing.
+ * Replaces: self.conv32x1(x) in Disp.forward and DispAgg.forward (models/GANet_deep.py:212, 232) -- MIOpen's implicit GEMM
+ *           with one output column, its transposes, and its weight gradient, which accumulates with atomics. */
+int ganet_disp_conv_workspace(int N, int C, int D, int H, int W);
+int ganet_disp_conv_forward(const float *x, const float *weight, float *y, int N, int C, int D, int H, int W, void *stream);
+int ganet_disp_conv_backward_data(const float *grad_y, const float *weight, float *grad_x,
+                                  int N, int C, int D, int H, int W, void *stream);
+int ganet_disp_conv_backward_weight(const float *x, const float *grad_y, float *workspace, float *grad_weight,
+                                    int N, int C, int D, int H, int W, void *stream);
 
 /* The end of SGABlock.forward (models/GANet_deep.py:270-277): behind `conv_refine` (Conv3d + BatchNorm3d, no ReLU) the
  * block adds its input back and applies ReLU,  `x += rem; return relu(x)`.  One pass:
