@@ -393,6 +393,180 @@ template <int GD> GA_DEV int seg_allmin_i(int v)
   return v;
 }
 
+// ---- 16-bit storage (mixed_kernels.h) ---------------------------------------------------------------------------------------
+// fp16 and bf16 values are held as uint16_t patterns; arithmetic is fp32 everywhere.  16 -> 32 is exact.  32 -> 16 rounds to
+// nearest even, keeps the sign of zero, overflows to +-inf, produces fp16 subnormals, and turns every NaN into ONE quiet NaN
+// (0x7E00 / 0x7FC0: no sign, no payload -- what the conversion instructions do with a payload differs from what a host does).
+// The gfx950 build uses the hardware conversions (v_cvt_f16_f32 / v_cvt_f32_f16 through _Float16, v_cvt_pk_bf16_f32, which has
+// no builtin); the emulator's compiler has no _Float16, so there -- and under -DGA_CVT_INTEGER on the device -- both are the
+// integer forms below.  tests/mixed_cases.py holds both builds to one table.
+#if defined(GA_HIPSIM)
+struct alignas(16) u4 { uint32_t x, y, z, w; };
+#else
+typedef uint4 u4;
+#endif
+#if defined(GA_HIPSIM) || defined(GA_CVT_INTEGER)
+#define GA_CVT_HW 0
+#else
+#define GA_CVT_HW 1
+#endif
+
+GA_DEV float bf16_to_f32(uint16_t h) { return i2f((int)((uint32_t)h << 16)); }
+
+GA_DEV uint16_t f32_to_bf16_int(float f)
+{
+  const uint32_t u = (uint32_t)f2i(f);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0;
+  return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);       // (a carry out of the mantissa is the next exponent, or inf)
+}
+
+GA_DEV uint16_t f32_to_f16_int(float f)
+{
+  const uint32_t u = (uint32_t)f2i(f), sign = (u >> 16) & 0x8000u, a = u & 0x7fffffffu;
+  if (a > 0x7f800000u) return 0x7e00;
+  if (a >= 0x47800000u) return (uint16_t)(sign | 0x7c00u);          // 2^16 and above, inf
+  if (a < 0x33000000u) return (uint16_t)sign;                       // below 2^-25: zero (2^-25 itself is a tie with an even zero)
+  if (a < 0x38800000u) {                                            // below 2^-14: a multiple of 2^-24
+    const uint32_t sh = 126u - (a >> 23), m = (a & 0x7fffffu) | 0x800000u;        // 14 <= sh <= 24
+    uint32_t h = m >> sh;
+    const uint32_t rest = m & ((1u << sh) - 1u), half = 1u << (sh - 1u);
+    if (rest > half || (rest == half && (h & 1u))) h++;             // (1023 + 1: the smallest normal)
+    return (uint16_t)(sign | h);
+  }
+  uint32_t h = (a - 0x38000000u) >> 13;
+  const uint32_t rest = a & 0x1fffu;
+  if (rest > 0x1000u || (rest == 0x1000u && (h & 1u))) h++;         // (a carry is the next exponent; 65520 and above: inf)
+  return (uint16_t)(sign | h);
+}
+
+GA_DEV float f16_to_f32_int(uint16_t h)
+{
+  const uint32_t sign = ((uint32_t)h & 0x8000u) << 16, e = ((uint32_t)h >> 10) & 31u, m = (uint32_t)h & 0x3ffu;
+  if (e == 31u) return i2f((int)(sign | 0x7f800000u | (m << 13)));
+  if (e == 0u) return i2f((int)(sign | (uint32_t)f2i((float)m * 5.9604644775390625e-08f)));     // m * 2^-24, exact
+  return i2f((int)(sign | ((e + 112u) << 23) | (m << 13)));
+}
+
+GA_DEV float f16_to_f32(uint16_t h)
+{
+#if GA_CVT_HW
+  return (float)__builtin_bit_cast(_Float16, h);
+#else
+  return f16_to_f32_int(h);
+#endif
+}
+
+GA_DEV uint16_t f32_to_f16(float f)
+{
+#if GA_CVT_HW
+  const uint16_t h = __builtin_bit_cast(uint16_t, (_Float16)f);
+  return f != f ? (uint16_t)0x7e00 : h;
+#else
+  return f32_to_f16_int(f);
+#endif
+}
+
+GA_DEV uint16_t f32_to_bf16(float f)
+{
+#if GA_CVT_HW
+  uint32_t r;
+  asm("v_cvt_pk_bf16_f32 %0, %1, %1" : "=v"(r) : "v"(f));
+  return f != f ? (uint16_t)0x7fc0 : (uint16_t)(r & 0xffffu);
+#else
+  return f32_to_bf16_int(f);
+#endif
+}
+
+// two values into one 32-bit word, the first in the low half
+GA_DEV uint32_t f32x2_to_bf16(float lo, float hi)
+{
+#if GA_CVT_HW
+  uint32_t r;
+  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+  if (lo != lo) r = (r & 0xffff0000u) | 0x7fc0u;
+  if (hi != hi) r = (r & 0x0000ffffu) | 0x7fc00000u;
+  return r;
+#else
+  return (uint32_t)f32_to_bf16_int(lo) | ((uint32_t)f32_to_bf16_int(hi) << 16);
+#endif
+}
+
+// storage types: T the element in memory, get / put its exact up-cast and its rounding, pack2 two values into a word
+struct st_f32 {
+  typedef float T;
+  static constexpr int CODE = 0;
+};
+struct st_f16 {
+  typedef uint16_t T;
+  static constexpr int CODE = 1;
+  static GA_DEV float get(uint16_t h) { return f16_to_f32(h); }
+  static GA_DEV uint16_t put(float f) { return f32_to_f16(f); }
+  static GA_DEV uint32_t pack2(float lo, float hi) { return (uint32_t)f32_to_f16(lo) | ((uint32_t)f32_to_f16(hi) << 16); }
+};
+struct st_bf16 {
+  typedef uint16_t T;
+  static constexpr int CODE = 2;
+  static GA_DEV float get(uint16_t h) { return bf16_to_f32(h); }
+  static GA_DEV uint16_t put(float f) { return f32_to_bf16(f); }
+  static GA_DEV uint32_t pack2(float lo, float hi) { return f32x2_to_bf16(lo, hi); }
+};
+// a copy of 16-bit patterns: the "value" is the pattern itself in the low half of a float register (bit moves only, no
+// floating-point instruction ever sees it)
+struct st_raw16 {
+  typedef uint16_t T;
+  static constexpr int CODE = -1;
+  static GA_DEV float get(uint16_t h) { return i2f((int)h); }
+  static GA_DEV uint16_t put(float f) { return (uint16_t)f2i(f); }
+  static GA_DEV uint32_t pack2(float lo, float hi) { return ((uint32_t)f2i(lo) & 0xffffu) | ((uint32_t)f2i(hi) << 16); }
+};
+
+// V = 8: 16-byte requests -- one for eight 16-bit elements, two for eight floats; V = 1: the scalar twin
+template <typename ST, int V> GA_DEV void st_load(const typename ST::T *p, float (&o)[V])
+{
+  if constexpr (sizeof(typename ST::T) == 4) {
+    if constexpr (V == 8) {
+      const f4 a = *reinterpret_cast<const f4 *>(p), b = *reinterpret_cast<const f4 *>(p + 4);
+      o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
+    } else {
+      o[0] = *p;
+    }
+  } else {
+    if constexpr (V == 8) {
+      const u4 a = *reinterpret_cast<const u4 *>(p);
+      const uint32_t w[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        o[2 * j] = ST::get((uint16_t)(w[j] & 0xffffu));
+        o[2 * j + 1] = ST::get((uint16_t)(w[j] >> 16));
+      }
+    } else {
+      o[0] = ST::get(*p);
+    }
+  }
+}
+
+template <typename ST, int V> GA_DEV void st_store(typename ST::T *p, const float (&o)[V])
+{
+  if constexpr (sizeof(typename ST::T) == 4) {
+    if constexpr (V == 8) {
+      f4 a, b;
+      a.x = o[0]; a.y = o[1]; a.z = o[2]; a.w = o[3]; b.x = o[4]; b.y = o[5]; b.z = o[6]; b.w = o[7];
+      *reinterpret_cast<f4 *>(p) = a;
+      *reinterpret_cast<f4 *>(p + 4) = b;
+    } else {
+      *p = o[0];
+    }
+  } else {
+    if constexpr (V == 8) {
+      u4 a;
+      a.x = ST::pack2(o[0], o[1]); a.y = ST::pack2(o[2], o[3]); a.z = ST::pack2(o[4], o[5]); a.w = ST::pack2(o[6], o[7]);
+      *reinterpret_cast<u4 *>(p) = a;
+    } else {
+      *p = ST::put(o[0]);
+    }
+  }
+}
+
 // MI355X: workgroup b runs on XCD b % 8 (observed, speed only).  Give each XCD a
 // contiguous range of logical blocks so neighbouring tiles share one L2.
 GA_DEV int xcd_remap(int b, int nb)

@@ -9,6 +9,7 @@
 #include "misc_kernels.h"
 #include "disp_tail_kernels.h"
 #include "disp_conv_kernels.h"
+#include "mixed_kernels.h"
 #include "sga_kernels.h"
 #include "sga_row_kernels.h"
 #include "sga_col_kernels.h"
@@ -1768,6 +1769,149 @@ GA_EXPORT int ganet_bn_apply_forward(const float *x, const float *rem, const flo
   if (vec) GA_LAUNCH((bn_affine_apply<4>), grid, dim3(BN_BLOCK), st, x, rem, scale, shift, y, g, relu);
   else GA_LAUNCH((bn_affine_apply<1>), grid, dim3(BN_BLOCK), st, x, rem, scale, shift, y, g, relu);
   return check_launch("batch norm apply");
+}
+
+// ---- mixed precision: 16-bit storage around the fp32 ops (mixed_kernels.h) ----------------------------------------------------
+namespace {
+bool type_code(int t) { return t == GANET_F32 || t == GANET_F16 || t == GANET_BF16; }
+
+template <typename Tx, typename Tr, typename Ty>
+void launch_bn_mixed(bool vec, dim3 grid, hipStream_t st, const void *x, const void *rem, const float *scale, const float *shift,
+                     void *y, const BnGeom &g, int relu)
+{
+  const typename Tx::T *xp = (const typename Tx::T *)x;
+  const typename Tr::T *rp = (const typename Tr::T *)rem;
+  typename Ty::T *yp = (typename Ty::T *)y;
+  if (vec) GA_LAUNCH((bn_affine_apply_mixed<Tx, Tr, Ty, MX_V>), grid, dim3(BN_BLOCK), st, xp, rp, scale, shift, yp, g, relu);
+  else GA_LAUNCH((bn_affine_apply_mixed<Tx, Tr, Ty, 1>), grid, dim3(BN_BLOCK), st, xp, rp, scale, shift, yp, g, relu);
+}
+
+template <typename T16>
+void launch_bn_mixed_of(bool rem16, bool y16, bool vec, dim3 grid, hipStream_t st, const void *x, const void *rem,
+                        const float *scale, const float *shift, void *y, const BnGeom &g, int relu)
+{
+  if (rem16 && y16) launch_bn_mixed<T16, T16, T16>(vec, grid, st, x, rem, scale, shift, y, g, relu);
+  else if (rem16) launch_bn_mixed<T16, T16, st_f32>(vec, grid, st, x, rem, scale, shift, y, g, relu);
+  else if (y16) launch_bn_mixed<T16, st_f32, T16>(vec, grid, st, x, rem, scale, shift, y, g, relu);
+  else launch_bn_mixed<T16, st_f32, st_f32>(vec, grid, st, x, rem, scale, shift, y, g, relu);
+}
+
+template <typename Ts, typename Td>
+void launch_cast(const void *src, void *dst, i64 n, hipStream_t st)
+{
+  const typename Ts::T *sp = (const typename Ts::T *)src;
+  typename Td::T *dp = (typename Td::T *)dst;
+  if (aligned16(src) && aligned16(dst) && n >= MX_V)
+    GA_LAUNCH((cast_kernel<Ts, Td, MX_V>), dim3(ew_grid(n / MX_V)), dim3(256), st, sp, dp, n);
+  else
+    GA_LAUNCH((cast_kernel<Ts, Td, 1>), dim3(ew_grid(n)), dim3(256), st, sp, dp, n);
+}
+
+template <typename Ts>
+void launch_cast_from(const void *src, void *dst, i64 n, int dst_type, bool same, hipStream_t st)
+{
+  if (dst_type == GANET_F32) launch_cast<Ts, st_f32>(src, dst, n, st);
+  else if (same) launch_cast<st_raw16, st_raw16>(src, dst, n, st);
+  else if (dst_type == GANET_F16) launch_cast<Ts, st_f16>(src, dst, n, st);
+  else launch_cast<Ts, st_bf16>(src, dst, n, st);
+}
+}  // namespace
+
+GA_EXPORT int ganet_cast(const void *src, void *dst, int n_hi, int n_lo, int src_type, int dst_type, void *stream)
+{
+  const char *who = "ganet_cast";
+  if (!src || !dst) return fail(GANET_E_INVALID, "%s: null pointer", who);
+  if (!type_code(src_type) || !type_code(dst_type)) return fail(GANET_E_INVALID, "%s: type code %d -> %d", who, src_type, dst_type);
+  if (n_hi < 0 || n_lo < 0) return fail(GANET_E_INVALID, "%s: negative count n_hi=%d n_lo=%d", who, n_hi, n_lo);
+  const i64 n = ((i64)n_hi << 31) + n_lo;
+  if (n <= 0) return fail(GANET_E_INVALID, "%s: non-positive count", who);
+  if (src == dst) return fail(GANET_E_INVALID, "%s: dst must not alias src", who);
+  hipStream_t st = (hipStream_t)stream;
+  const bool same = src_type == dst_type;
+  if (src_type == GANET_F32) launch_cast_from<st_f32>(src, dst, n, dst_type, same, st);
+  else if (src_type == GANET_F16) launch_cast_from<st_f16>(src, dst, n, dst_type, same, st);
+  else launch_cast_from<st_bf16>(src, dst, n, dst_type, same, st);
+  return check_launch("cast");
+}
+
+GA_EXPORT int ganet_bn_apply_forward_mixed(const void *x, const void *rem, const float *scale, const float *shift, void *y, int N,
+                                           int C, int S, int relu, int x_type, int rem_type, int y_type, void *stream)
+{
+  const char *who = "ganet_bn_apply_forward_mixed";
+  if (!x || !scale || !shift || !y) return fail(GANET_E_INVALID, "%s: null pointer", who);
+  if (!type_code(x_type) || !type_code(rem_type) || !type_code(y_type))
+    return fail(GANET_E_INVALID, "%s: type codes x=%d rem=%d y=%d", who, x_type, rem_type, y_type);
+  if (y == rem) return fail(GANET_E_INVALID, "%s: y may alias x, not rem", who);
+  if (y == x && (y_type == GANET_F32) != (x_type == GANET_F32))
+    return fail(GANET_E_INVALID, "%s: y may alias x only where both have one width", who);
+  const bool rem16 = rem != nullptr && rem_type != GANET_F32, y16 = y_type != GANET_F32, x32 = x_type == GANET_F32;
+  if (x32 && !y16)
+    return fail(GANET_E_UNSUPPORTED, "%s: x and y are fp32: that is ganet_bn_apply_forward's case", who);
+  if (x32 && rem16)
+    return fail(GANET_E_UNSUPPORTED, "%s: no kernel for an fp32 x with a 16-bit rem", who);
+  if (!x32 && ((rem16 && rem_type != x_type) || (y16 && y_type != x_type)))
+    return fail(GANET_E_UNSUPPORTED, "%s: no kernel for x=%d rem=%d y=%d: 16-bit rem and y have x's format", who, x_type, rem_type, y_type);
+  const bool vec = S % MX_V == 0 && aligned16(x) && aligned16(y) && aligned16(rem);
+  BnGeom g;
+  GA_TRY(bn_geom(who, N, C, S, false, false, &g));
+  const int cap = bn_rows_cap(C);
+  const i64 want = ((vec ? S / MX_V : S) + BN_BLOCK - 1) / BN_BLOCK;
+  g.Rs = (int)(want < cap ? want : cap);
+  g.Rn = cap / g.Rs < N ? cap / g.Rs : N;
+  const dim3 grid(g.Rs * g.Rn, C);
+  hipStream_t st = (hipStream_t)stream;
+  if (x32 && y_type == GANET_F16) launch_bn_mixed<st_f32, st_f32, st_f16>(vec, grid, st, x, rem, scale, shift, y, g, relu);
+  else if (x32) launch_bn_mixed<st_f32, st_f32, st_bf16>(vec, grid, st, x, rem, scale, shift, y, g, relu);
+  else if (x_type == GANET_F16) launch_bn_mixed_of<st_f16>(rem16, y16, vec, grid, st, x, rem, scale, shift, y, g, relu);
+  else launch_bn_mixed_of<st_bf16>(rem16, y16, vec, grid, st, x, rem, scale, shift, y, g, relu);
+  return check_launch("batch norm apply (mixed)");
+}
+
+GA_EXPORT int ganet_cost_volume_forward_16(const void *x, const void *y, void *cost, int N, int C, int Dn, int H, int W,
+                                           void *stream)
+{
+  const char *who = "ganet_cost_volume_forward_16";
+  if (!x || !y || !cost) return fail(GANET_E_INVALID, "%s: null pointer", who);
+  if (N <= 0 || C <= 0 || Dn <= 0 || H <= 0 || W <= 0) return fail(GANET_E_INVALID, "%s: non-positive size", who);
+  if (cost == x || cost == y) return fail(GANET_E_INVALID, "%s: cost must not alias an input", who);
+  const i64 n = (i64)N * 2 * C * Dn * H * W;
+  const uint16_t *xp = (const uint16_t *)x, *yp = (const uint16_t *)y;
+  uint16_t *cp = (uint16_t *)cost;
+  if (W % MX_V == 0 && aligned16(x) && aligned16(cost))
+    GA_LAUNCH(cost_volume_fwd16, dim3(ew_grid(n / MX_V)), dim3(256), (hipStream_t)stream, xp, yp, cp, N, C, Dn, H, W);
+  else
+    GA_LAUNCH(cost_volume_fwd16s, dim3(ew_grid(n)), dim3(256), (hipStream_t)stream, xp, yp, cp, N, C, Dn, H, W);
+  return check_launch("cost volume forward (16-bit)");
+}
+
+GA_EXPORT int ganet_l1_normalize_forward_mixed(const void *x, float *y0, float *y1, float *y2, float *y3, int N, int G, int C,
+                                               int K, int H, int W, int x_type, void *stream)
+{
+  const char *who = "ganet_l1_normalize_forward_mixed";
+  GA_TRY(check_norm(who, N, G, C, K, H, W));
+  float *ys[4] = {y0, y1, y2, y3};
+  if (!x) return fail(GANET_E_INVALID, "%s: null pointer", who);
+  if (!type_code(x_type)) return fail(GANET_E_INVALID, "%s: type code %d", who, x_type);
+  if (x_type == GANET_F32) return fail(GANET_E_UNSUPPORTED, "%s: x is fp32: that is ganet_l1_normalize_forward's case", who);
+  NormPtrs p = {};
+  for (int g = 0; g < 4; g++) {
+    if (g < G && !ys[g]) return fail(GANET_E_INVALID, "%s: null output %d", who, g);
+    p.y[g] = ys[g < G ? g : 0];
+  }
+  const i64 HW = (i64)H * W;
+  const dim3 grid(ew_grid((i64)N * G * C * HW)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  const uint16_t *xp = (const uint16_t *)x;
+  if (x_type == GANET_F16) {
+    if (K == 5) GA_LAUNCH((l1norm_fwd_mixed<5, st_f16>), grid, block, st, xp, p, N, G, C, K, HW);
+    else if (K == 75) GA_LAUNCH((l1norm_fwd_mixed<75, st_f16>), grid, block, st, xp, p, N, G, C, K, HW);
+    else GA_LAUNCH((l1norm_fwd_mixed<0, st_f16>), grid, block, st, xp, p, N, G, C, K, HW);
+  } else {
+    if (K == 5) GA_LAUNCH((l1norm_fwd_mixed<5, st_bf16>), grid, block, st, xp, p, N, G, C, K, HW);
+    else if (K == 75) GA_LAUNCH((l1norm_fwd_mixed<75, st_bf16>), grid, block, st, xp, p, N, G, C, K, HW);
+    else GA_LAUNCH((l1norm_fwd_mixed<0, st_bf16>), grid, block, st, xp, p, N, G, C, K, HW);
+  }
+  return check_launch("l1 normalise forward (mixed)");
 }
 
 // ---- image front and back end (predict.py:75-114, :132-138; dataloader/dataset.py:48-92) --------------------------------------

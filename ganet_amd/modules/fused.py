@@ -249,7 +249,7 @@ class DispConv(Module):
     conv = nn.Conv3d(C, 1, (3,3,3), (1,1,1), (1,1,1), bias=False), C <= 64.  The module holds the convolution it was given and
     reads conv.weight at every call: the parameter object, its state_dict key and whatever the optimizer holds do not move.
     `directions`: which of "forward", "data" (gradient of the input), "weight" (gradient of the weight) run on the HIP kernels;
-    the others stay on ATen."""
+    the others stay on ATen.  An fp16 / bf16 input is handed to the convolution itself."""
 
     def __init__(self, conv, directions=DispConvFunction.ALL):
         super().__init__()
@@ -268,6 +268,10 @@ class DispConv(Module):
         self.directions = directions
 
     def forward(self, x):
+        if x.dtype in (torch.float16, torch.bfloat16):
+            # mixed-precision inference (torch.autocast): the kernels are fp32, a 16-bit input is the wrapped convolution's.  The
+            # class's forward, not the instance's: harness.fuse rebinds the instance's to this module.
+            return type(self.conv).forward(self.conv, x)
         return DispConvFunction.apply(x.contiguous(), self.conv.weight.contiguous(), self.directions)
 
 

@@ -20,13 +20,20 @@ use_fused_disp_conv (opt-in, composes with all of the above in any order):
   conv32x1          models/GANet_deep.py:212, 232  Conv3d(32, 1, 3, 1, 1) in Disp and DispAgg -> DispConv: streaming HIP kernels instead
                                                    of MIOpen's one-column GEMM; the rebind is on the convolution INSTANCE, so whichever
                                                    forward its owner has calls it
+use_mixed_precision (opt-in, inference; applies use_fused_ops and use_fused_bn where they have not been):
+  every site between a convolution and a guided-aggregation op on 16-bit storage, for torch.autocast: see the function
 """
 import types
 
 import torch
 
+from ganet_amd.functions import mixed as mixed_fn
+from ganet_amd.functions.fused import (LgaRegressFunction, SoftminFunction, normalize_filters, normalize_guidance,
+                                       sga_forward_infer)
+from ganet_amd.functions.GANet import Lga2Function, LgaFunction
 from ganet_amd.modules.fused import (BnRelu, DispAggTail, DispConv, DispTail, GuidedSGA, GuidedSGABnRelu, ResidualBnRelu, SoftminDisparityRegression,
-                                     TrilinearUpsample)
+                                     TrilinearUpsample, folded_bn)
+from ganet_amd.modules.mixed import MixedBnRelu
 
 _UP = TrilinearUpsample()
 
@@ -119,6 +126,219 @@ def use_fused_disp_tail(model):
 
 def _conv32x1_forward(self, x):
     return self._fused_conv(x)
+
+
+# ---- mixed precision: 16-bit convolutions around the fp32 guided-aggregation ops (inference) --------------------------------------
+
+_HALF = (torch.float16, torch.bfloat16)
+# the BasicConv whose output is an SGABlock's x, by the names of CostAggregation (models/GANet_deep.py:318-357, GANet11.py:287-303):
+# a Conv2x stands for its conv2
+_SGA_PRODUCER = {"sga1": "conv_start", "sga11": "conv1a", "sga12": "deconv2a", "sga2": "deconv1a", "sga13": "conv1b",
+                 "sga14": "deconv2b", "sga3": "deconv1b"}
+
+
+class _CastArmBnRelu:
+    """the cast arm of a BatchNorm site: the fp32 op on .float() inputs, then .to(out_dtype)"""
+
+    def __init__(self, bn, relu, out_dtype):
+        self.op, self.out_dtype = BnRelu(bn, relu=relu), out_dtype
+
+    def __call__(self, x, rem=None):
+        y = self.op(x.float(), rem.float() if rem is not None else None)
+        return y.to(self.out_dtype if self.out_dtype is not None else x.dtype)
+
+
+class _MixedOps:
+    """what the rebound forwards call at each site: the 16-bit-storage kernels (kernels=True) or the cast arm -- the existing
+    fp32 op between ATen casts (kernels=False: the fallback, the tests' yardstick and the baseline of the measurement)"""
+
+    def __init__(self, kernels):
+        self.kernels = bool(kernels)
+
+    def bn(self, bn, relu, out_dtype=None):
+        return MixedBnRelu(bn, relu=relu, out_dtype=out_dtype) if self.kernels else _CastArmBnRelu(bn, relu, out_dtype)
+
+    def cast(self, t, dtype):
+        return mixed_fn.cast(t.contiguous(), dtype) if self.kernels else t.to(dtype)
+
+    def guidance(self, g, channels):
+        if self.kernels:
+            return mixed_fn.normalize_guidance_mixed(g.contiguous(), channels)
+        return normalize_guidance(g.float(), channels)
+
+    def filters(self, g):
+        return mixed_fn.normalize_filters_mixed(g.contiguous()) if self.kernels else normalize_filters(g.float())
+
+    def cost_volume(self, cv, x, y):
+        if self.kernels:
+            return mixed_fn.cost_volume_16(x.contiguous(), y.contiguous(), cv.maxdisp)     # (the module holds maxdisp + 1)
+        return type(cv).forward(cv, x.float(), y.float()).to(x.dtype)
+
+
+def _inference_only(m):
+    if m.training or torch.is_grad_enabled():
+        raise RuntimeError(f"use_mixed_precision is for inference: {type(m).__name__} met a 16-bit tensor in training mode or with "
+                           "autograd on (model.eval() under torch.no_grad(), as harness.steps.predict does)")
+
+
+def _mixed_basicconv_forward(self, x):
+    t = self.conv(x)
+    if t.dtype in _HALF:
+        _inference_only(self)
+        return self._mixed_bn(t)          # bn + relu on 16-bit storage, rounded once to this site's output type
+    return self._fused_bn(t)              # autocast off: BnRelu as before
+
+
+def _mixed_sgablock_forward(self, x, g):
+    if g.dtype not in _HALF:
+        return _sgablock_forward(self, x, g)
+    _inference_only(self)
+    mx = self._mixed
+    if x.dtype != torch.float32:          # (a producer this file does not know: SGA is fp32)
+        x = mx.cast(x, torch.float32)
+    rem = x
+    ks = mx.guidance(g, x.shape[1])       # 16-bit guidance -> four fp32 weight volumes, one pass
+    with torch.autocast("cuda", enabled=False):
+        fold = folded_bn(self.bn_relu[0]) if self.refine else ()
+    x = sga_forward_infer(x, *ks, *fold)  # fp32 in and out, unchanged
+    if not self.refine:
+        return self._fused_tail(x, rem)
+    x = self.conv_refine.conv(x)          # autocast rounds SGA's fp32 output for the convolution (DESIGN: out of scope)
+    return self._mixed_tail(x, rem) if x.dtype in _HALF else self._fused_tail(x, rem)
+
+
+def _mixed_cv_forward(self, x, y):
+    if x.dtype in _HALF:
+        return self._mixed.cost_volume(self, x, y)
+    return type(self).forward(self, x, y)
+
+
+def _mixed_top_conv_forward(self, x):
+    c = type(self).forward(self, x)       # GANet.conv_refine: [N,32,H/3,W/3], small; the bilinear up-sampling behind it is
+    return self._mixed.cast(c, torch.float32) if c.dtype in _HALF else c      # fp32 under autocast (ATen would cast it there)
+
+
+def _mixed_top_bn_relu_forward(self, x):
+    # GANet.bn_relu = Sequential(BatchNorm2d, ReLU) behind the up-sampling: fp32 in, and the concatenation and the convolution
+    # behind it want 16 bits -- one pass that rounds on the store, instead of an fp32 result that ATen casts twice
+    if x.is_cuda and x.dtype == torch.float32 and torch.is_autocast_enabled("cuda"):
+        _inference_only(self)
+        return self._mixed_bn(x, torch.get_autocast_dtype("cuda"))
+    if x.dtype in _HALF:
+        _inference_only(self)
+        return self._mixed_bn(x, x.dtype)
+    return type(self).forward(self, x)
+
+
+class _TopBnRelu:
+    """the BatchNorm + ReLU of GANet.bn_relu on either arm: (x fp32 | 16-bit, out_dtype 16-bit)"""
+
+    def __init__(self, bn, kernels):
+        self.bn, self.kernels = bn, kernels
+        self.op = BnRelu(bn, relu=True)
+
+    def __call__(self, x, out_dtype):
+        if self.kernels:
+            return MixedBnRelu(self.bn, relu=True, out_dtype=out_dtype, inplace=False)(x)
+        return self.op(x.float()).to(out_dtype)
+
+
+def _conv32x1_f32(self, x):
+    c = self.conv32x1(x)                  # [N,1,D,H,W]: small; the tails are fp32
+    return self._mixed.cast(c, torch.float32) if c.dtype in _HALF else c
+
+
+def _up_size(self, x):
+    return [self.maxdisp + 1, x.size()[3] * 3, x.size()[4] * 3]
+
+
+def _mixed_dispagg_forward(self, x, lg1, lg2):
+    mx, tail = self._mixed, self._fused_tail
+    v = torch.squeeze(_UP(_conv32x1_f32(self, x), _up_size(self, x)), 1)
+    if lg1.dtype not in _HALF:
+        return tail(v, lg1, lg2)
+    _inference_only(self)
+    assert lg1.size() == lg2.size()
+    f1, f2 = mx.filters(lg1), mx.filters(lg2)
+    v = Lga2Function.apply(v, f1, tail.radius)                        # DispAggTail.forward on filters normalised from 16 bits
+    v = SoftminFunction.apply(v.contiguous())
+    v = LgaFunction.apply(v, f2, tail.radius)
+    return LgaRegressFunction.apply(v, f2, tail.radius, tail.ndisp)
+
+
+def _mixed_disp_forward(self, x):
+    c, tail = _conv32x1_f32(self, x), self._fused_tail
+    if isinstance(tail, DispTail):
+        return tail(c)
+    return tail(torch.squeeze(_UP(c, _up_size(self, x)), 1))
+
+
+def use_mixed_precision(model, dtype=torch.bfloat16, kernels=True):
+    """Prepares GANet_deep / GANet11 for inference under torch.autocast("cuda", dtype=dtype) -- harness.steps.predict(..., amp=dtype):
+    MIOpen's convolutions run in 16 bits, SGA, LGA and the tails stay fp32 as they are, and the sites between them run on
+    16-bit storage (ganet_amd.modules.mixed / functions.mixed) so that no ATen cast pass stands between a convolution and one
+    of our ops.  Applies use_fused_ops and use_fused_bn first where the model has not been rebound; helpers stay out of the
+    module tree (no state_dict key moves).  Rebinds:
+      BasicConv (use_bn)   a 16-bit convolution output -> MixedBnRelu; fp32 (autocast off) -> the BnRelu it had
+      ... in front of an SGABlock (conv_start, conv1a, the conv2 of the Conv2x before an sga*): out_dtype fp32 -- SGA's x
+      SGABlock             guidance through normalize_guidance_mixed, SGA on sga_forward_infer (fp32), the tail
+                           MixedBnRelu(t 16-bit, rem fp32) -> 16-bit
+      GANet.cv             MixedGetCostVolume's kernel
+      DispAgg              filters through normalize_filters_mixed; conv32x1's output up-cast by `cast` in front of TrilinearUpsample
+      Disp                 the same up-cast (training only: never reached in inference)
+      GANet.conv_refine    its small 16-bit output up-cast by `cast`: torch.autocast runs the bilinear up-sampling behind it in fp32
+      GANet.bn_relu        Sequential(BatchNorm2d, ReLU) behind that up-sampling: fp32 in, 16-bit out in one pass (MixedBnRelu), so
+                           that the concatenation and the Guidance convolution behind it see 16 bits
+    kernels=False rebinds the same sites to the cast arm: the existing fp32 op on .float() inputs followed by .to(out_dtype).
+    `dtype` is what the model is prepared for; the sites themselves follow the tensors they meet.  Returns the number of sites."""
+    if dtype not in _HALF:
+        raise TypeError(f"use_mixed_precision: dtype is torch.bfloat16 or torch.float16, got {dtype}")
+    mods = list(model.modules())
+    if not any("_fused_sga" in m.__dict__ for m in mods if type(m).__name__ == "SGABlock"):
+        use_fused_ops(model)
+    if not any("_fused_bn" in m.__dict__ for m in mods if type(m).__name__ == "BasicConv"):
+        use_fused_bn(model)
+    mx = _MixedOps(kernels)
+    to_f32 = set()
+    for m in mods:
+        if type(m).__name__ == "CostAggregation":
+            for sga, producer in _SGA_PRODUCER.items():
+                p = getattr(m, producer, None)
+                if hasattr(m, sga) and p is not None:
+                    to_f32.add(id(p.conv2 if type(p).__name__ == "Conv2x" else p))
+    n = 0
+    for m in mods:
+        kind = type(m).__name__
+        # (object.__setattr__: the helpers stay out of the module tree, state_dict keys do not move)
+        if kind == "BasicConv" and m.use_bn:
+            object.__setattr__(m, "_mixed_bn", mx.bn(m.bn, bool(m.relu), torch.float32 if id(m) in to_f32 else None))
+            m.forward = types.MethodType(_mixed_basicconv_forward, m)
+            n += 1
+        elif kind == "SGABlock":
+            object.__setattr__(m, "_mixed", mx)
+            object.__setattr__(m, "_mixed_tail", mx.bn(m.conv_refine.bn if m.refine else m.bn, True))
+            m.forward = types.MethodType(_mixed_sgablock_forward, m)
+            n += 1
+        elif kind == "GetCostVolume":
+            object.__setattr__(m, "_mixed", mx)
+            m.forward = types.MethodType(_mixed_cv_forward, m)
+            n += 1
+        elif kind in ("Disp", "DispAgg"):
+            object.__setattr__(m, "_mixed", mx)
+            m.forward = types.MethodType(_mixed_dispagg_forward if kind == "DispAgg" else _mixed_disp_forward, m)
+            n += 1
+        elif kind == "GANet":
+            conv, seq = getattr(m, "conv_refine", None), getattr(m, "bn_relu", None)
+            if isinstance(conv, torch.nn.Conv2d):
+                object.__setattr__(conv, "_mixed", mx)
+                conv.forward = types.MethodType(_mixed_top_conv_forward, conv)
+                n += 1
+            if isinstance(seq, torch.nn.Sequential) and len(seq) == 2 and isinstance(seq[0], torch.nn.modules.batchnorm._BatchNorm) \
+                    and isinstance(seq[1], torch.nn.ReLU):
+                object.__setattr__(seq, "_mixed_bn", _TopBnRelu(seq[0], mx.kernels))
+                seq.forward = types.MethodType(_mixed_top_bn_relu_forward, seq)
+                n += 1
+    return n
 
 
 def use_fused_disp_conv(model, directions=("forward", "data", "weight")):

@@ -2,7 +2,7 @@
 """BASELINE.json configs[2]: full GANet-deep inference (9 GA layers... 7 SGA + 2 LGA2) on a KITTI-2015-sized pair
 (1248x384, max_disp 192) on one MI355X, the reference's model on this repository's ops.
 
-    python -m harness.infer [--model GANet_deep] [--height 384] [--width 1248] [--max_disp 192] [--fused] [--fused_bn] [--fused_conv32] [--iters 5]
+    python -m harness.infer [--model GANet_deep] [--height 384] [--width 1248] [--max_disp 192] [--fused] [--fused_bn] [--fused_conv32] [--amp bf16|fp16 [--amp_cast_arm]] [--iters 5]
 
 Prints one JSON line: ms per forward pass (median of --iters, HIP events), peak device memory, parameter count.
 Random-init weights and synthetic standardised images (no checkpoint / dataset offline); predict.py:100-114 is the
@@ -36,6 +36,9 @@ def main():
     ap.add_argument("--fused", action="store_true", help="ganet_amd.modules.fused op chains instead of the stock call forms")
     ap.add_argument("--fused_bn", action="store_true", help="BatchNorm + ReLU behind every BasicConv on ganet_amd.modules.fused.BnRelu")
     ap.add_argument("--fused_conv32", action="store_true", help="conv32x1 of every Disp / DispAgg on ganet_amd.modules.fused.DispConv (HIP kernels instead of MIOpen)")
+    ap.add_argument("--amp", choices=("bf16", "fp16"), default=None,
+                    help="mixed-precision inference: 16-bit convolutions under torch.autocast around the fp32 GA ops (harness.fuse.use_mixed_precision; implies --fused --fused_bn)")
+    ap.add_argument("--amp_cast_arm", action="store_true", help="with --amp: the cast arm (fp32 ops between ATen casts) instead of the 16-bit-storage kernels")
     ap.add_argument("--no_miopen_find", dest="miopen_find", action="store_false",
                     help="MIOpen immediate mode (heuristic solver choice) instead of timing its solvers per shape")
     ap.add_argument("--kernel_share", action="store_true", help="add the per-group device-time table (torch.profiler over 2 extra passes)")
@@ -52,16 +55,18 @@ def main():
     n_fused = fuse.use_fused_ops(model) if args.fused else 0
     n_fused_bn = fuse.use_fused_bn(model) if args.fused_bn else 0
     n_fused_conv32 = fuse.use_fused_disp_conv(model) if args.fused_conv32 else 0
+    amp = {"bf16": torch.bfloat16, "fp16": torch.float16, None: None}[args.amp]
+    n_mixed = fuse.use_mixed_precision(model, amp, kernels=not args.amp_cast_arm) if amp is not None else 0
     left, right, _ = steps.synthetic_batch(args.batch, args.height, args.width, args.max_disp, dev)
     for _ in range(args.warmup):
-        out = steps.predict(model, left, right)
+        out = steps.predict(model, left, right, amp)
     torch.cuda.synchronize()
     torch.cuda.reset_peak_memory_stats()
     times = []
     for _ in range(args.iters):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        out = steps.predict(model, left, right)
+        out = steps.predict(model, left, right, amp)
         e1.record()
         e1.synchronize()
         times.append(e0.elapsed_time(e1))
@@ -70,7 +75,7 @@ def main():
     share = None
     if args.kernel_share:
         from harness.kernel_share import profile_passes
-        share = profile_passes(lambda: steps.predict(model, left, right), 2)
+        share = profile_passes(lambda: steps.predict(model, left, right, amp), 2)
     print(json.dumps({
         "what": "full-model inference, reference model on the drop-in ops", "model": args.model,
         "input": [args.batch, 3, args.height, args.width], "max_disp": args.max_disp,
@@ -79,7 +84,9 @@ def main():
         "fused_conv32": "DispConv (%d call sites)" % n_fused_conv32 if args.fused_conv32 else False,
         "ms_per_pair": round(times[len(times) // 2], 3), "ms_min": round(times[0], 3), "iters": args.iters,
         "peak_mem_GB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 3),
-        "miopen_find": bool(args.miopen_find), "params": sum(p.numel() for p in model.parameters()), "dtype": "f32", "weights": "random init",
+        "miopen_find": bool(args.miopen_find), "params": sum(p.numel() for p in model.parameters()),
+        "amp": ("%s, %s (%d call sites)" % (args.amp, "cast arm" if args.amp_cast_arm else "16-bit-storage kernels", n_mixed)) if amp is not None else None,
+        "dtype": ("%s convolutions under autocast, f32 guided aggregation and tails" % args.amp) if amp is not None else "f32", "weights": "random init",
         "disp_range": [round(float(out.min()), 3), round(float(out.max()), 3)],
         "device": torch.cuda.get_device_name(0), "kernel_share": share}))
 

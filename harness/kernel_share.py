@@ -17,6 +17,9 @@ def classify(name):
         return "BatchNorm"
     if re.search(r"upsample|interpolat", low):
         return "interpolation"
+    if re.search(r"direct_copy_kernel|copy_kernel|_to_copy", low):
+        # under --amp: what autocast and the cast arm spend on aten._to_copy (fp32 <-> 16-bit), plus ATen's plain copies
+        return "copies and dtype casts (aten copy kernels)"
     return "other PyTorch kernels"
 
 

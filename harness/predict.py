@@ -38,6 +38,9 @@ def parse_args(argv=None):
     ap.add_argument("--fused", action="store_true", help="ganet_amd.modules.fused op chains instead of the stock call forms")
     ap.add_argument("--fused_bn", action="store_true", help="BatchNorm + ReLU behind every BasicConv on ganet_amd.modules.fused.BnRelu")
     ap.add_argument("--host_io", action="store_true", help="the reference's host-side numpy front and back end instead of the kernels")
+    ap.add_argument("--amp", choices=("bf16", "fp16"), default=None,
+                    help="mixed-precision inference: 16-bit convolutions under torch.autocast around the fp32 GA ops (harness.fuse.use_mixed_precision)")
+    ap.add_argument("--amp_cast_arm", action="store_true", help="with --amp: the cast arm (fp32 ops between ATen casts) instead of the 16-bit-storage kernels")
     args = ap.parse_args(argv)
     if args.crop_height <= 0 or args.crop_width <= 0 or args.max_disp <= 0:
         ap.error("--crop_height, --crop_width and --max_disp are positive")
@@ -133,6 +136,8 @@ def main(argv=None):
         steps.load_checkpoint(args.resume, model)
     n_fused = fuse.use_fused_ops(model) if args.fused else 0
     n_fused_bn = fuse.use_fused_bn(model) if args.fused_bn else 0
+    amp = {"bf16": torch.bfloat16, "fp16": torch.float16, None: None}[args.amp]
+    n_mixed = fuse.use_mixed_precision(model, amp, kernels=not args.amp_cast_arm) if amp is not None else 0
 
     def clock():
         torch.cuda.synchronize()
@@ -146,7 +151,7 @@ def main(argv=None):
         from ganet_amd.modules.fused import DisparityOutput, StereoInput
         l, r, hw = StereoInput(*crop)(torch.from_numpy(left).to(dev), torch.from_numpy(right).to(dev))
     t1 = clock()
-    pred = steps.predict(model, l, r)
+    pred = steps.predict(model, l, r, amp)
     t2 = clock()
     if args.host_io:
         u16 = host_back(pred.cpu().numpy(), hw)
@@ -160,6 +165,8 @@ def main(argv=None):
         "io": "host numpy (predict.py's order of work)" if args.host_io else "ganet_amd.modules.fused.StereoInput / DisparityOutput",
         "ops": "ganet_amd.modules.fused (%d call sites)" % n_fused if args.fused else "drop-in call forms (libs/)",
         "fused_bn": "BnRelu (%d call sites)" % n_fused_bn if args.fused_bn else False,
+        "amp": ("%s, %s (%d call sites)" % (args.amp, "cast arm" if args.amp_cast_arm else "16-bit-storage kernels", n_mixed)) if amp is not None else None,
+        "dtype": ("%s convolutions under autocast, f32 guided aggregation and tails" % args.amp) if amp is not None else "f32",
         "ms_io_front": round(1e3 * (t1 - t0), 3), "ms_model_first_call": round(1e3 * (t2 - t1), 3), "ms_io_back": round(1e3 * (t3 - t2), 3),
         "weights": args.resume or "random init", "disp_u16_range": [int(u16.min()), int(u16.max())],
         "device": torch.cuda.get_device_name(0)}))

@@ -107,18 +107,26 @@ def train_step(model, optimizer, name, left, right, target, max_disp, crit, fuse
 
 
 @torch.no_grad()
-def predict(model, left, right):
-    """predict.py:107-114."""
+def predict(model, left, right, amp=None):
+    """predict.py:107-114.  amp: torch.bfloat16 | torch.float16 runs the pass under torch.autocast("cuda", dtype=amp) -- the
+    convolutions in 16 bits -- for a model prepared by harness.fuse.use_mixed_precision; the images are rounded to `amp` once,
+    by ganet_amd.functions.mixed.cast, instead of once per convolution that reads them."""
     model.eval()
-    return model(left, right)
+    if amp is None:
+        return model(left, right)
+    if left.is_cuda and left.dtype == torch.float32 and right.dtype == torch.float32:
+        from ganet_amd.functions.mixed import cast
+        left, right = cast(left.contiguous(), amp), cast(right.contiguous(), amp)
+    with torch.autocast("cuda", dtype=amp):
+        return model(left, right)
 
 
-def predict_images(model, left_u8, right_u8, crop_hw):
+def predict_images(model, left_u8, right_u8, crop_hw, amp=None):
     """predict.py:92-138 from two uint8 images [H, W, 3 | 4] on the device to the uint16 [h, w] disparity image it saves:
-    StereoInput -> predict -> DisparityOutput, no numpy on the pixel path."""
+    StereoInput -> predict -> DisparityOutput, no numpy on the pixel path.  amp: see predict."""
     from ganet_amd.modules.fused import DisparityOutput, StereoInput
     left, right, hw = StereoInput(*crop_hw)(left_u8, right_u8)
-    return DisparityOutput()(predict(model, left, right), hw)
+    return DisparityOutput()(predict(model, left, right, amp), hw)
 
 
 def synthetic_batch(batch, height, width, max_disp, device, seed=123):

@@ -379,6 +379,36 @@ int ganet_bn_train_backward(const float *x, const float *rem, const float *grad_
 int ganet_bn_apply_forward(const float *x, const float *rem, const float *scale, const float *shift, float *y,
                            int N, int C, int S, int relu, void *stream);
 
+/* ---------------------------------------------------------------- mixed precision - */
+
+/* ABI v14 (additions).  Inference with 16-bit convolutions around fp32 guided aggregation: the streaming ops between a
+ * convolution and a GA op on 16-bit STORAGE, fp32 arithmetic inside (ganet_amd/csrc/mixed_kernels.h).  fp16 and bf16 values
+ * are uint16_t patterns; a *_type argument names the format of one buffer. */
+#define GANET_F32 0
+#define GANET_F16 1
+#define GANET_BF16 2
+/* The contract: with 16-bit inputs, op_mixed(a16, ..) == convert(op_fp32(upcast(a16), ..), out_type) bit for bit, where op_fp32
+ * is ganet_bn_apply_forward / ganet_cost_volume_forward / ganet_l1_normalize_forward of the same build: the up-cast is exact,
+ * the arithmetic is the fp32 kernel's expression, the result is rounded once.
+ *   convert      32 -> 16 rounds to nearest even, keeps the sign of zero, overflows to +-inf, produces fp16 subnormals; every NaN
+ *                becomes the one quiet NaN 0x7E00 (fp16) / 0x7FC0 (bf16).  16 -> 32 is exact.
+ *   cast         dst[i] = convert(src[i]) for i < n = n_hi * 2^31 + n_lo (the ABI's scalars are ints; 0 <= n_lo), between any two
+ *                of the three types; the same type is a copy of patterns.  dst must not alias src.
+ *   bn apply     y = relu(scale[c] x + shift[c] [+ rem]) on [N, C, S] as ganet_bn_apply_forward; x fp16 | bf16; rem NULL, fp32 or
+ *                x's format; y fp32 or x's format.  Also an fp32 x (rem NULL or fp32) with a 16-bit y: behind an op that autocast
+ *                runs in fp32.  y may alias x where both have one width and never otherwise, and never rem.
+ *   cost volume  ganet_cost_volume_forward on 2-byte elements: a copy of patterns with zeros (0x0000 is zero in both formats).
+ *   l1 normalize ganet_l1_normalize_forward with an fp16 | bf16 x and fp32 outputs.
+ * 16-byte requests (eight 16-bit elements) where the inner size is a multiple of 8 and the bases are 16-byte aligned, scalar
+ * ones otherwise.  NULL, non-positive sizes, an unknown type code, a forbidden alias: GANET_E_INVALID.  A type combination that
+ * is not compiled (fp32 x and y, an fp32 x with a 16-bit rem, two different 16-bit formats in one call): GANET_E_UNSUPPORTED. */
+int ganet_cast(const void *src, void *dst, int n_hi, int n_lo, int src_type, int dst_type, void *stream);
+int ganet_bn_apply_forward_mixed(const void *x, const void *rem, const float *scale, const float *shift, void *y,
+                                 int N, int C, int S, int relu, int x_type, int rem_type, int y_type, void *stream);
+int ganet_cost_volume_forward_16(const void *x, const void *y, void *cost, int N, int C, int Dn, int H, int W, void *stream);
+int ganet_l1_normalize_forward_mixed(const void *x, float *y0, float *y1, float *y2, float *y3,
+                                     int N, int G, int C, int K, int H, int W, int x_type, void *stream);
+
 /* ---------------------------------------------------------------- image I/O ------ */
 
 /* ABI v14.  The two ends around the model: a stereo pair of uint8 images becomes the model's standardised fp32 input, the
