@@ -79,6 +79,8 @@ def use_fused_ops(model):
             m.forward = types.MethodType(_dispagg_forward, m)
             n += 1
         elif kind == "Disp":
+            if isinstance(m.__dict__.get("_fused_tail"), DispTail):
+                continue                  # use_fused_disp_tail came first: its one op replaces the pair below, in either order
             object.__setattr__(m, "_fused_tail", SoftminDisparityRegression(m.maxdisp))
             m.forward = types.MethodType(_disp_forward, m)
             n += 1
@@ -111,9 +113,9 @@ def _disp_tail_forward(self, x):
 
 
 def use_fused_disp_tail(model):
-    """Every Disp (the two auxiliary disparities of training) on DispTail.  Alone, or after use_fused_ops, whose
-    TrilinearUpsample -> SoftminDisparityRegression pair it replaces; DispAgg is not touched.  Returns the number of call
-    sites rebound."""
+    """Every Disp (the two auxiliary disparities of training) on DispTail.  Alone, or with use_fused_ops in either order: it
+    replaces that function's TrilinearUpsample -> SoftminDisparityRegression pair, and use_fused_ops leaves a Disp that holds a
+    DispTail alone; DispAgg is not touched.  Returns the number of call sites rebound."""
     n = 0
     for m in model.modules():
         if type(m).__name__ == "Disp":

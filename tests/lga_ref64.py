@@ -100,9 +100,11 @@ def _gamma(n):
     return n * U / (1.0 - n * U)
 
 
-def chain_bound(x, f, gy, r, passes):
+def chain_bound(x, f, gy, r, passes, backward=True):
     """A first-order rounding-error bound, per element, for an fp32 evaluation of lga_chain: -> dict(y, gx, gf) of bounds, and
     `want`, the float64 chain they belong to.  Whoever compares allows a factor 2 for the second-order terms, as with SGA.
+    backward=False (a call that got no gradient): the forward chain and the bound of y alone -- the same y and the same bound,
+    without the adjoint passes, which are most of the cost.
 
     u = 2^-24.  A sum of n rounded products, accumulated in any order (fused or not, split over lanes or not), differs from
     the exact sum of the same terms by at most gamma_n sum|terms|, gamma_n = n u / (1 - n u) (every term passes through at
@@ -126,16 +128,26 @@ def chain_bound(x, f, gy, r, passes):
     Everything is computed from the float64 chain beside it, from the inputs alone."""
     fa = np.abs(np.asarray(f, np.float64))
     T, D = f.shape[-3], x.shape[-3]
-    want = lga_chain(x, f, gy, r, passes)
+    if backward:
+        want = lga_chain(x, f, gy, r, passes)
+    else:
+        ins = [np.asarray(x, np.float64)]
+        for _ in range(passes):
+            ins.append(lga_forward(ins[-1], f, r))
+        want = {"y": ins[-1], "ins": ins[:-1]}
     gT, gN = _gamma(T), _gamma(D + passes)
     E = [np.zeros(x.shape)]
     for k in range(passes):
-        E.append(lga_forward(E[k], fa, r) + gT * lga_forward(np.abs(want["ins"][k]), fa, r))
+        # (E_0 = 0 pushes nothing through: the pass over it is skipped, its result is 0 exactly)
+        E.append((lga_forward(E[k], fa, r) if k else 0.0) + gT * lga_forward(np.abs(want["ins"][k]), fa, r))
+    if not backward:
+        return {"y": E[passes], "want": want}
     g, G, egf = np.asarray(gy, np.float64), np.zeros(x.shape), 0.0
     for k in reversed(range(passes)):
         xk = np.abs(want["ins"][k])
-        through, own = lga_backward(xk, fa, G, r), lga_backward(xk, fa, np.abs(g), r)
-        egf = egf + through[1] + lga_backward(E[k], fa, np.abs(g), r)[1] + gN * own[1]
+        own = lga_backward(xk, fa, np.abs(g), r)
+        through = lga_backward(xk, fa, G, r) if k < passes - 1 else (0.0, 0.0)      # (G_P = 0, E_0 = 0: exact zeros, skipped)
+        egf = egf + through[1] + (lga_backward(E[k], fa, np.abs(g), r)[1] if k else 0.0) + gN * own[1]
         G = through[0] + gT * own[0]
         g = lga_backward(want["ins"][k], f, g, r)[0]
     return {"y": E[passes], "gx": G, "gf": egf, "want": want}

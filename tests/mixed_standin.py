@@ -1,25 +1,15 @@
 """TEST INFRASTRUCTURE: a tiny stereo network with the class and attribute names harness.fuse looks for (BasicConv, Conv2x,
 SGABlock, CostAggregation, DispAgg, GetCostVolume; conv_start / conv1a / deconv1a / sga1 / sga11 / sga2 / disp1 / cv), so that
-use_mixed_precision can be run end to end on the device where the reference's model files are not available.  Only the
-containers have a forward of their own; SGABlock and DispAgg have none -- the rebound forwards are the thing under test."""
+use_mixed_precision can be run end to end on the device where the reference's model files are not available.  BasicConv,
+SGABlock and DispAgg are those of tests/standin_net.py (which has the training-capable network); here the rebound forwards
+are the thing under test, at 4 channels, one level and inference only."""
 import torch
 from torch import nn
 
 from ganet_amd.modules.GANet import GetCostVolume
+from standin_net import BasicConv, DispAgg, SGABlock      # noqa: F401  (the blocks are tests/standin_net.py's)
 
 C = 4            # channels of the cost-aggregation volumes
-
-
-class BasicConv(nn.Module):
-    def __init__(self, cin, cout, is_3d=False, relu=True, **kw):
-        super().__init__()
-        self.relu, self.use_bn = relu, True
-        self.conv = (nn.Conv3d if is_3d else nn.Conv2d)(cin, cout, bias=False, **kw)
-        self.bn = (nn.BatchNorm3d if is_3d else nn.BatchNorm2d)(cout)
-
-    def forward(self, x):
-        x = self.bn(self.conv(x))
-        return torch.relu(x) if self.relu else x
 
 
 class Conv2x(nn.Module):
@@ -32,29 +22,14 @@ class Conv2x(nn.Module):
         return self.conv2(torch.cat((self.conv1(x), rem), 1))
 
 
-class SGABlock(nn.Module):
-    def __init__(self, c=C):
-        super().__init__()
-        self.refine = True
-        self.bn_relu = nn.Sequential(nn.BatchNorm3d(c), nn.ReLU(inplace=True))
-        self.conv_refine = BasicConv(c, c, True, relu=False, kernel_size=3, padding=1)
-
-
-class DispAgg(nn.Module):
-    def __init__(self, maxdisp):
-        super().__init__()
-        self.maxdisp = maxdisp
-        self.conv32x1 = nn.Conv3d(C, 1, (3, 3, 3), (1, 1, 1), (1, 1, 1), bias=False)
-
-
 class CostAggregation(nn.Module):
     def __init__(self, maxdisp):
         super().__init__()
         self.conv_start = BasicConv(16, C, True, relu=False, kernel_size=3, padding=1)
         self.conv1a = BasicConv(C, C, True, kernel_size=3, padding=1)
         self.deconv1a = Conv2x(C, relu=False)
-        self.sga1, self.sga11, self.sga2 = SGABlock(), SGABlock(), SGABlock()
-        self.disp1 = DispAgg(maxdisp)
+        self.sga1, self.sga11, self.sga2 = SGABlock(C, True), SGABlock(C, True), SGABlock(C, True)
+        self.disp1 = DispAgg(maxdisp, C)
 
     def forward(self, x, g):
         x = self.sga1(self.conv_start(x), g["sg1"])

@@ -1,11 +1,13 @@
 """TEST INFRASTRUCTURE: every guided-aggregation op call of a MODEL run, held to the float64 statement of its operation --
-shared by tests/test_model_calls_cpu.py (the CPU-oracle twin: the yardstick alone, and its teeth) and
-tests/test_gpu_model_calls.py (the product, call by call).
+shared by tests/test_model_calls_cpu.py (the CPU-oracle twin: the yardstick alone, and its teeth),
+tests/test_gpu_model_calls.py (the product, call by call, on the reference's models) and tests/test_gpu_standin_calls.py (the same
+on the stand-in network of tests/standin_net.py, which needs no reference file: `run_model` takes any ready model and the
+rebinders of harness.fuse to apply, in a given order).
 
 Why: the per-op case tables feed inputs of magnitude about 1 and hold gradients to parity_cases.TOL = 1e-4 ABSOLUTE; a model
 drives the ops with gradients of 1e-2 .. 1e-4, where that bar lets an all-zero LGA2 data gradient through.  The float64
-statements (sga_ref64, lga_ref64.chain_bound, misc_ref64, bn_ref64, loss_ref64) scale with the data, so they are applied
-here to the tensors a model run really hands to each op.
+statements (sga_ref64, lga_ref64.chain_bound, misc_ref64, bn_ref64, loss_ref64, disp_tail_ref64, disp_conv_ref64) scale with
+the data, so they are applied here to the tensors a model run really hands to each op.
 
 `recording` wraps forward / backward of a list of autograd Functions (and plain launch functions) for its duration and keeps
 one `Record` per call: kind, arguments (host copies of the tensors, cloned BEFORE the call), outputs, incoming and returned
@@ -25,12 +27,19 @@ disparities up to 192 and becomes 1e-4 * (D - 1) / 192 (`_atol_px`).  The relati
 import collections
 import contextlib
 import inspect
+import types
 
 import numpy as np
 import torch
 
 import bn_cases
 import bn_ref64
+import disp_conv_cases
+import disp_conv_ref64
+import disp_tail_cases
+import disp_tail_ref64
+import io_cases
+import io_ref64
 import lga_ref64
 import loss_cases
 import loss_ref64
@@ -152,41 +161,54 @@ def recording(monkeypatch, functions, plain=()):
 
 
 def product_functions():
-    """everything in ganet_amd.functions.GANet.__all__, every Function of ganet_amd.functions.fused, and the two plain
-    functions that launch a kernel without one"""
+    """everything in ganet_amd.functions.GANet.__all__, every Function of ganet_amd.functions.fused, and the plain functions
+    that launch a kernel without one: the two inference forms of SGA and the image front and back end"""
     import ganet_amd.functions.fused as ff
     import ganet_amd.functions.GANet as fg
     import ganet_amd.modules.fused as mf
     fns = [getattr(fg, n) for n in fg.__all__]
     fns += [v for v in vars(ff).values() if isinstance(v, type) and issubclass(v, torch.autograd.Function) and v.__module__ == ff.__name__]
-    return fns, [((fg, ff), "_sga_infer"), ((ff, mf), "sga_forward_infer")]
+    return fns, [((fg, ff), "_sga_infer"), ((ff, mf), "sga_forward_infer"), ((ff, mf), "stereo_input"), ((ff, mf), "window_f32"),
+                 ((ff, mf), "disparity_to_u16")]
 
 
-def run_product(monkeypatch, name, crop, max_disp, device, fused_ops=False, fused_bn=False, seed=0):
-    """The product model (harness.steps.build_model on the drop-in `libs/`, optionally with harness.fuse's call sites) under
-    the recorder: steps.predict under no_grad, then one training step -- steps.loss_mix on the stock call forms, the fused
-    DisparityLoss on the fused ones.  crop = (H, W, B).  -> (records of predict, records of the training step)"""
+REBINDERS = ("use_fused_ops", "use_fused_bn", "use_fused_disp_tail", "use_fused_disp_conv")
+
+
+def run_model(monkeypatch, model, batch, max_disp, rebinders=(), name="GANet_deep", fused_loss=None):
+    """A ready model (already on its device) under the recorder: `rebinders` -- names of harness.fuse's functions out of REBINDERS
+    -- applied in the order given (each must find a site), then steps.predict under no_grad, then one training step:
+    steps.loss_mix on the stock call forms, the fused DisparityLoss on the fused ones (fused_loss: default, whether anything
+    was rebound).  batch = (left, right, target).  -> (records of predict, records of the training step)"""
     from ganet_amd.modules.fused import DisparityLoss
     from harness import fuse, steps
-    H, W, B = crop
-    torch.manual_seed(seed)
-    model = steps.build_model(name, max_disp, device)
-    if fused_ops:
-        assert fuse.use_fused_ops(model) > 0
-    if fused_bn:
-        assert fuse.use_fused_bn(model) > 0
-    left, right, target = steps.synthetic_batch(B, H, W, max_disp, device)
+    for rb in rebinders:
+        assert rb in REBINDERS, rb
+        assert getattr(fuse, rb)(model) > 0, rb
+    fused_loss = bool(rebinders) if fused_loss is None else fused_loss
+    left, right, target = batch
     with recording(monkeypatch, *product_functions()) as records:
         steps.predict(model, left, right)
         n_infer = len(records)
         model.train()
         outs = model(left, right)
-        if fused_ops:
+        if fused_loss:
             loss, _ = DisparityLoss.for_model(name, max_disp)(outs, target)
         else:
             loss = steps.loss_mix(name, outs, target, target < max_disp, steps.criterion(True))
         loss.backward()
     return records[:n_infer], records[n_infer:]
+
+
+def run_product(monkeypatch, name, crop, max_disp, device, fused_ops=False, fused_bn=False, seed=0):
+    """The product model (harness.steps.build_model on the drop-in `libs/`, optionally with harness.fuse's call sites) through
+    run_model.  crop = (H, W, B).  -> (records of predict, records of the training step)"""
+    from harness import steps
+    H, W, B = crop
+    torch.manual_seed(seed)
+    model = steps.build_model(name, max_disp, device)
+    rebinders = (("use_fused_ops",) if fused_ops else ()) + (("use_fused_bn",) if fused_bn else ())
+    return run_model(monkeypatch, model, steps.synthetic_batch(B, H, W, max_disp, device), max_disp, rebinders, name, fused_loss=fused_ops)
 
 
 def oracle_functions():
@@ -202,6 +224,9 @@ DECLARED = {
     "BnReluFunction": lambda r: {"arg4", "arg5"},                              # running_mean / running_var, as F.batch_norm does
     "_sga_infer": lambda r: {"arg5"},                                          # `output`
     "DisparityLossFunction": lambda r: {"arg2"},                               # the fp64 workspace
+    "stereo_input": lambda r: {"arg6", "arg7"},                                # out_left / out_right, where given
+    # UpSoftminRegressionFunction and DispConvFunction declare nothing written ("neither is written"; their workspaces are
+    # their own): no entry, any write is reported
 }
 
 
@@ -307,9 +332,16 @@ def sga_judge(R, got, equality=True, what=""):
 
 
 def reference_of(r, oracle):
-    """the float64 side of an SGA / LGA record, computed once and kept on the record"""
+    """the float64 side of an SGA / LGA / DispTail / DispConv record, computed once and kept on the record"""
     if r.reference is None:
-        r.reference = sga_reference(r, oracle) if r.kind in ("SgaFunction", "OracleSga") else lga_reference(r)
+        if r.kind in ("SgaFunction", "OracleSga"):
+            r.reference = sga_reference(r, oracle)
+        elif r.kind == "UpSoftminRegressionFunction":
+            r.reference = tail_reference(r)
+        elif r.kind == "DispConvFunction":
+            r.reference = conv_reference(r)
+        else:
+            r.reference = lga_reference(r)
     return r.reference
 
 
@@ -352,10 +384,12 @@ def _lga_inputs(r):
 
 
 def lga_reference(r):
-    """lga_ref64.chain_bound on the recorded x, f and incoming gradient (no gradient came in: zeros, and only y is compared)"""
+    """lga_ref64.chain_bound on the recorded x, f and incoming gradient (no gradient came in: the forward chain, and only y is
+    compared)"""
     x, f, radius, passes = _lga_inputs(r)
-    gy = r.grad_out[0] if r.grad_out is not None else np.zeros_like(x)
-    return lga_ref64.chain_bound(x, f, gy, radius, passes)
+    if r.grad_out is None:
+        return lga_ref64.chain_bound(x, f, None, radius, passes, backward=False)
+    return lga_ref64.chain_bound(x, f, r.grad_out[0], radius, passes)
 
 
 def lga_got(r):
@@ -602,6 +636,100 @@ def check_myloss2(r, oracle=None):
     return q
 
 
+# ---- the Disp tails: DispTail and DispConv -----------------------------------------------------------------------------------------
+# Both bars are the case tables' own, unchanged: twice a first-order bound that is computed FROM the data it is applied to
+# (disp_tail_ref64: every term is u or an ulp of lambda times sums of |x|, slopes of x, p |od - out|, |gv|; disp_conv_ref64:
+# L u sum |terms|).  Nothing in them assumes magnitude 1 or dyadic inputs -- those belong to the tables' "exact" kinds, which are
+# not applied here -- so on recorded data (a convolution output of 1e-1, gradients of 1e-4 .. 1e-6) they scale down with it and
+# need no restating.  tests/test_model_calls_cpu.py calibrates them on such data against disp_tail_ref64.Float32Model (both
+# variants of lambda), resp. an fp32 accumulation of the convolution, never against the device's results.
+def _volume(x):
+    return x.reshape((x.shape[0],) + x.shape[-3:])
+
+
+def tail_reference(r):
+    """disp_tail_ref64.Statement on the recorded c, size and incoming gradient (none came in: zeros, and only out is compared)"""
+    x, size = r.args
+    c = _volume(x)
+    size = tuple(int(v) for v in size)
+    g = r.grad_out[0] if r.grad_out is not None else np.zeros((c.shape[0],) + size[1:], np.float32)
+    return disp_tail_ref64.Statement(c, size, np.ascontiguousarray(g, np.float32))
+
+
+def tail_got(r):
+    got = {"out": r.outputs[0]}
+    if r.grad_in is not None:
+        got["grad_x"] = _volume(r.grad_in[0])
+    return got
+
+
+def tail_judge(S, got, what=""):
+    """|got - float64| <= twice the statement's bound per element of out and grad_x: disp_tail_cases.check -> key -> error / bar"""
+    case = types.SimpleNamespace(id=what, kind="general", ref=S)
+    return disp_tail_cases.check(case, {k: np.ascontiguousarray(v) for k, v in got.items()}, quantities=tuple(got), verbose=False)
+
+
+def check_up_softmin_regression(r, oracle=None):
+    return tail_judge(reference_of(r, oracle), tail_got(r), repr(r))
+
+
+def conv_reference(r):
+    """disp_conv_ref64.Statement on the recorded x, weight and incoming gradient (none came in: zeros, and only y is compared)"""
+    x, w = r.args[:2]
+    gy = _volume(r.grad_out[0]) if r.grad_out is not None else np.zeros((x.shape[0],) + x.shape[2:], np.float32)
+    return disp_conv_ref64.Statement(x, w, np.ascontiguousarray(gy, np.float32))
+
+
+def conv_got(r):
+    got = {"y": _volume(r.outputs[0])}
+    if r.grad_in is not None:
+        C = r.args[0].shape[1]
+        for key, g, shape in (("grad_x", r.grad_in[0], r.args[0].shape), ("grad_weight", r.grad_in[1], (C, 3, 3, 3))):
+            if g is not None:                        # (autograd did not ask for it)
+                got[key] = g.reshape(shape)
+    return got
+
+
+def conv_judge(S, got, what=""):
+    """|got - float64| <= 2 L u sum |terms| per element of y, grad_x and grad_weight: disp_conv_cases.check.  A direction the
+    record's `directions` leaves on ATen is held to the same bound (its L is never more than the number of terms)"""
+    case = types.SimpleNamespace(id=what, kind="general", ref=S)
+    return disp_conv_cases.check(case, {k: np.ascontiguousarray(v) for k, v in got.items()}, quantities=tuple(got), verbose=False)
+
+
+def check_disp_conv(r, oracle=None):
+    if r.grad_in is not None:
+        assert r.grad_in[1] is not None, (repr(r), "the convolution's weight got no gradient")
+    return conv_judge(reference_of(r, oracle), conv_got(r), repr(r))
+
+
+# ---- the image front and back end: io_ref64's statement (a), bit for bit, as io_cases holds the kernels to it ------------------------
+def _same_bits(name, got, want):
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape and got.dtype == want.dtype, (name, got.shape, want.shape, got.dtype, want.dtype)
+    bad = io_cases.bits(got) != io_cases.bits(want) if got.dtype == np.float32 else got != want
+    assert not bad.any(), (name, f"{int(bad.sum())} of {bad.size} elements differ from the statement")
+    return 0.0
+
+
+def check_stereo_input(r, oracle=None):
+    """equality needs io_cases' premise: every occurring quotient at least io_ref64.MARGIN from a rounding boundary of float32"""
+    left, right, crop, oy, oxl, oxr = r.args[:6]
+    assert io_ref64.margin(left, right) >= io_ref64.MARGIN, (repr(r), "a quotient sits at a rounding boundary: draw other images")
+    want = io_ref64.stereo_input(left, right, int(crop[0]), int(crop[1]), int(oy), int(oxl), int(oxr))
+    return {"left": _same_bits("left", r.outputs[0], want[0]), "right": _same_bits("right", r.outputs[1], want[1])}
+
+
+def check_window_f32(r, oracle=None):
+    src, crop, oy, ox, sub, fill = r.args
+    return {"dst": _same_bits("dst", r.outputs[0], io_ref64.window_f32(src, int(crop[0]), int(crop[1]), int(oy), int(ox), sub, fill))}
+
+
+def check_disparity_to_u16(r, oracle=None):
+    disp, hw, oy, ox, scale = r.args
+    return {"u16": _same_bits("u16", r.outputs[0], io_ref64.disparity_u16(disp, int(hw[0]), int(hw[1]), int(oy), int(ox), scale))}
+
+
 CHECKERS = {
     "SgaFunction": check_sga, "OracleSga": check_sga, "_sga_infer": check_sga_infer, "sga_forward_infer": check_sga_infer,
     "OracleLgaChain": check_lga, **{k: check_lga for k in LGA_PASSES},
@@ -611,6 +739,8 @@ CHECKERS = {
     "TrilinearUpsampleFunction": check_trilinear, "LgaRegressFunction": check_lga_regress,
     "ResidualReluFunction": check_residual_relu, "BnApplyFunction": check_bn_apply, "BnReluFunction": check_bn_relu,
     "DisparityLossFunction": check_disparity_loss, "MyLoss2Function": check_myloss2,
+    "UpSoftminRegressionFunction": check_up_softmin_regression, "DispConvFunction": check_disp_conv,
+    "stereo_input": check_stereo_input, "window_f32": check_window_f32, "disparity_to_u16": check_disparity_to_u16,
 }
 
 
