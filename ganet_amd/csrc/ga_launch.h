@@ -4,7 +4,9 @@
 #pragma once
 #include "ga_common.h"
 #include "sga_row_kernels.h"
+#include <stdint.h>
 #include <stdio.h>
+#include <type_traits>
 
 #if defined(GA_HIPSIM)
 #define GA_LAUNCH(kern, grid, block, stream, ...) \
@@ -45,6 +47,38 @@ inline void ga_note_stale_error()
 
 namespace ga {
 
+// ---- runtime facts -> template arguments ------------------------------------------------------------------
+// A launch site is written ONCE, inside a generic lambda; these helpers call it with the runtime values as constants:
+//   with_flags([&](auto asc, auto full) { GA_LAUNCH((kern<decltype(asc)::value, decltype(full)::value>), ...); }, dir == 0, D % dpl == 0);
+// Every combination the helper can produce is instantiated; a kernel compiled for fewer keeps an `if constexpr` in the lambda.
+template <int V> using int_c = std::integral_constant<int, V>;
+template <class T> struct type_c { using type = T; };
+
+template <bool... Cs, class F> void with_flags(F &&f) { f(std::bool_constant<Cs>{}...); }
+template <bool... Cs, class F, class... Bs> void with_flags(F &&f, bool b, Bs... rest)
+{
+  b ? with_flags<Cs..., true>(f, rest...) : with_flags<Cs..., false>(f, rest...);
+}
+
+// f(int_c<V>) for the V of the list that equals v; false (and no call) where none does
+template <int... Vs, class F> bool with_int(int v, F &&f) { return ((v == Vs && (f(int_c<Vs>{}), true)) || ...); }
+// the same with a value for everything else
+template <int Else, int... Vs, class F> void with_int_else(int v, F &&f) { with_int<Vs...>(v, f) || (f(int_c<Else>{}), true); }
+// f(int_c<V>) where the vector path applies, f(int_c<1>) where it does not
+template <int V, class F> void with_width(bool vec, F &&f) { with_int_else<1, V>(vec ? V : 1, f); }
+// f(type_c<T>) for the i-th type of the list; the last one stands for every larger i
+template <class T, class... Ts, class F> void with_type(int i, F &&f)
+{
+  if constexpr (sizeof...(Ts) == 0) f(type_c<T>{});
+  else if (i == 0) f(type_c<T>{});
+  else with_type<Ts...>(i - 1, f);
+}
+
+// alignment facts of the operands (a null pointer counts as aligned)
+template <class... P> bool aligned16(const P *...p) { return (((((uintptr_t)p) & 15) == 0) && ...); }
+inline bool aligned4(const void *p) { return ((uintptr_t)p & 3) == 0; }
+inline bool aligned8(const void *p) { return ((uintptr_t)p & 7) == 0; }
+
 // rows per wavefront (LN) x positions per staged batch (SBH): LDS per wave bounds residency
 #ifndef GA_ROW_LN_F
 #define GA_ROW_LN_F 1
@@ -67,6 +101,14 @@ inline int row_dpl(int D)
   GA_ROW_DPLS(X)
 #undef X
   return best;
+}
+// f(int_c<DPL>) for the compiled DPL that equals dpl
+template <class F> bool with_row_dpl(int dpl, F &&f)
+{
+#define X(P) if (dpl == (P)) { f(int_c<P>{}); return true; }
+  GA_ROW_DPLS(X)
+#undef X
+  return false;
 }
 
 // adjoint scan: 1 tile + mask per row

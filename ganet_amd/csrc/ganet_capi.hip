@@ -48,6 +48,22 @@ int check_launch(const char *what)
   return GANET_OK;
 }
 
+// the argument checks the entries share: one helper per message form
+template <class... P> int check_ptrs(const char *who, const P *...p)
+{
+  return ((p == nullptr) || ...) ? fail(GANET_E_INVALID, "%s: null pointer", who) : GANET_OK;
+}
+template <class... I> int check_positive(const char *who, I... n)
+{
+  return ((n <= 0) || ...) ? fail(GANET_E_INVALID, "%s: non-positive size", who) : GANET_OK;
+}
+int check_ncdhw(const char *who, int N, int C, int D, int H, int W)
+{
+  if (N > 0 && C > 0 && D > 0 && H > 0 && W > 0) return GANET_OK;
+  return fail(GANET_E_INVALID, "%s: non-positive size N=%d C=%d D=%d H=%d W=%d", who, N, C, D, H, W);
+}
+int check_dir(const char *who, int dir) { return dir < 0 || dir > 3 ? fail(GANET_E_INVALID, "%s: dir %d", who, dir) : GANET_OK; }
+
 #define GA_TRY(expr)                         \
   do {                                       \
     const int rc_ = (expr);                  \
@@ -81,29 +97,45 @@ struct Options {
 Options g_opt;
 std::once_flag g_opt_once;
 
-// the one place an option value is normalised: ganet_set_option and the environment go through it (GANET_LGA_WAVE=-1
-// from the environment used to be stored as is, truthy, and reported as -1)
+// the one list of options: ganet_set_option, ganet_get_option and the environment go through it, and `norm` is the one place a
+// value is normalised (GANET_LGA_WAVE=-1 from the environment used to be stored as is, truthy, and reported as -1)
+int norm_tri(int v) { return v < 0 ? 0 : (v > 2 ? 2 : v); }
+int norm_flag(int v) { return v ? 1 : 0; }
+int norm_count(int v) { return v < 0 ? 0 : v; }
+const struct OptionDesc {
+  const char *name;
+  std::atomic<int> Options::*field;
+  int (*norm)(int);
+} g_option_table[] = {
+    {"GANET_LGA_WAVE", &Options::lga_wave, norm_tri},
+    {"GANET_SGA_TILED", &Options::sga_tiled, norm_flag},
+    {"GANET_LGA_MIX", &Options::lga_mix, norm_count},      // 1: S = SIMDs of the device; n > 1: S = n (tests)
+    {"GANET_LGA_SEGS", &Options::lga_segs, norm_count},
+    {"GANET_SGA_WIDE_SCAN", &Options::wide_scan, norm_tri},
+    {"GANET_SGA_WIDE_COL", &Options::wide_col, norm_tri},
+    {"GANET_SGA_ROWWAVE", &Options::rowwave, norm_flag},
+    {"GANET_SGA_COLBLOCK", &Options::colblock, norm_flag},
+};
+
+const OptionDesc *find_option(const char *name)
+{
+  for (const OptionDesc &o : g_option_table)
+    if (!strcmp(name, o.name)) return &o;
+  return nullptr;
+}
+
 bool store_option(const char *name, int value)
 {
-  auto tri = [](int v) { return v < 0 ? 0 : (v > 2 ? 2 : v); };
-  if (!strcmp(name, "GANET_LGA_WAVE")) g_opt.lga_wave = tri(value);
-  else if (!strcmp(name, "GANET_SGA_TILED")) g_opt.sga_tiled = value ? 1 : 0;
-  else if (!strcmp(name, "GANET_LGA_MIX")) g_opt.lga_mix = value < 0 ? 0 : value;      // 1: S = SIMDs of the device; n > 1: S = n (tests)
-  else if (!strcmp(name, "GANET_LGA_SEGS")) g_opt.lga_segs = value > 0 ? value : 0;
-  else if (!strcmp(name, "GANET_SGA_WIDE_SCAN")) g_opt.wide_scan = tri(value);
-  else if (!strcmp(name, "GANET_SGA_WIDE_COL")) g_opt.wide_col = tri(value);
-  else if (!strcmp(name, "GANET_SGA_ROWWAVE")) g_opt.rowwave = value ? 1 : 0;
-  else if (!strcmp(name, "GANET_SGA_COLBLOCK")) g_opt.colblock = value ? 1 : 0;
-  else return false;
-  return true;
+  const OptionDesc *o = find_option(name);
+  if (o) g_opt.*o->field = o->norm(value);
+  return o != nullptr;
 }
 
 void load_env_options()
 {
-  for (const char *name : {"GANET_LGA_WAVE", "GANET_SGA_TILED", "GANET_LGA_SEGS", "GANET_LGA_MIX", "GANET_SGA_WIDE_SCAN",
-                           "GANET_SGA_WIDE_COL", "GANET_SGA_ROWWAVE", "GANET_SGA_COLBLOCK"}) {
-    const char *v = getenv(name);
-    if (v && *v) store_option(name, atoi(v));
+  for (const OptionDesc &o : g_option_table) {
+    const char *v = getenv(o.name);
+    if (v && *v) store_option(o.name, atoi(v));
   }
 }
 const Options &opts()
@@ -141,7 +173,25 @@ bool pick_pair(int D, int want_gd, int *gd, int *dpl)
   return true;
 }
 
-bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+// f(int_c<GD>, int_c<DPL>) for the compiled pair that equals (gd, dpl)
+template <class F> bool with_sga_pair(int gd, int dpl, F &&f)
+{
+#define X(G, P) if (gd == (G) && dpl == (P)) { f(int_c<G>{}, int_c<P>{}); return true; }
+  GA_SGA_PAIRS(X)
+#undef X
+  return false;
+}
+
+// blocks of `per_block` items for `count` of them, at least one and at most `cap`
+int clamp_grid(i64 count, int per_block, i64 cap)
+{
+  const i64 g = (count + per_block - 1) / per_block;
+  return (int)(g < 1 ? 1 : (g < cap ? g : cap));
+}
+int px_grid(i64 npix) { return clamp_grid(npix, 256, 256 * 32); }
+int ew_grid(i64 n) { return clamp_grid(n, 256, 256 * 16); }
+
+int device_cus();
 
 ScanGeom make_geom(int S, int D, int H, int W, int dir, bool backward)
 {
@@ -166,7 +216,7 @@ int launch_scan_fwd(const float *x, const float *g, float *A, int S, int D, int 
                     hipStream_t st)
 {
   ScanGeom geo = make_geom(S, D, H, W, dir, false);
-  const bool rowvec = DPL <= 17 && dir >= 2 && (W % 4 == 0) && aligned16(x) && aligned16(g) && aligned16(A);
+  const bool rowvec = DPL <= 17 && dir >= 2 && (W % 4 == 0) && aligned16(x, g, A);
   const int block = dir < 2 ? 128 : 64;      // (measured defaults of round 1, profiles/r1_tune_sga.txt)
   const int lpb = block / GD;
   const int grid = (geo.total_lines + lpb - 1) / lpb;
@@ -185,8 +235,7 @@ int launch_scan_bwdg(const float *g, const uint8_t *mask, const uint16_t *kp, co
                      float *G, int S, int D, int H, int W, int dir, hipStream_t st)
 {
   ScanGeom geo = make_geom(S, D, H, W, dir, true);
-  const bool rowvec = DPL <= 17 && dir >= 2 && (W % 4 == 0) && aligned16(g) && aligned16(gout) &&
-                      aligned16(G) && (((uintptr_t)mask & 3) == 0) && (((uintptr_t)kp & 7) == 0);
+  const bool rowvec = DPL <= 17 && dir >= 2 && (W % 4 == 0) && aligned16(g, gout, G) && aligned4(mask) && aligned8(kp);
   const int block = dir < 2 ? 128 : 64;      // (measured defaults of round 1, profiles/r1_tune_sga.txt)
   const int lpb = block / GD;
   const int grid = (geo.total_lines + lpb - 1) / lpb;
@@ -217,8 +266,7 @@ int launch_scan_bwdg_f32mask(const float *g, const float *mask, const uint16_t *
 
 int check_dims5(const char *who, int N, int C, int D, int H, int W)
 {
-  if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0)
-    return fail(GANET_E_INVALID, "%s: non-positive size N=%d C=%d D=%d H=%d W=%d", who, N, C, D, H, W);
+  GA_TRY(check_ncdhw(who, N, C, D, H, W));
   if ((i64)D * H * W > 0x7fffffffLL / 4 || (i64)N * C * H > 0x7fffffffLL || (i64)N * C * W > 0x7fffffffLL)
     return fail(GANET_E_UNSUPPORTED, "%s: slice too large for 32-bit line indexing", who);
   return GANET_OK;
@@ -250,24 +298,26 @@ bool colblock_ok(int D, int W, int dir, size_t smem)
   return opts().colblock && dir < 2 && W % 4 == 0 && D <= 16 * 13 && smem <= ROW_SMEM_MAX;
 }
 
+ColGeom col_geom(int D, int H, int W, int out_mode, int tiled)
+{
+  ColGeom geo;
+  geo.D = D; geo.H = H; geo.W = W; geo.HW = (i64)H * W; geo.out_mode = out_mode; geo.tiled = tiled;
+  return geo;
+}
+
 int col_fwd(const float *x, const float *g, float *A, int S, int D, int H, int W, int dir, hipStream_t st,
             int out_mode = 0)
 {
-  ColGeom geo;
-  geo.D = D; geo.H = H; geo.W = W; geo.HW = (i64)H * W; geo.out_mode = out_mode; geo.tiled = 0;
+  const ColGeom geo = col_geom(D, H, W, out_mode, 0);
   const int dpl = row_dpl(D);
   const bool full = dpl > 0 && D % dpl == 0;
   const size_t smem = col_smem_fwd(D);
   const dim3 grid((W + COL_NC - 1) / COL_NC, S), block(256);
-#define X(P)                                                                                        \
-  if (dpl == (P)) {                                                                                 \
-    if (dir == 0 && full) GA_LAUNCH_SMEM((sga_col_fwd<P, true, true>), grid, block, smem, st, x, g, A, geo);      \
-    else if (dir == 0) GA_LAUNCH_SMEM((sga_col_fwd<P, true, false>), grid, block, smem, st, x, g, A, geo);        \
-    else if (full) GA_LAUNCH_SMEM((sga_col_fwd<P, false, true>), grid, block, smem, st, x, g, A, geo);            \
-    else GA_LAUNCH_SMEM((sga_col_fwd<P, false, false>), grid, block, smem, st, x, g, A, geo);                     \
-  }
-  GA_ROW_DPLS(X)
-#undef X
+  with_row_dpl(dpl, [&](auto P) {
+    with_flags([&](auto asc, auto fl) {
+      GA_LAUNCH_SMEM((sga_col_fwd<decltype(P)::value, decltype(asc)::value, decltype(fl)::value>), grid, block, smem, st, x, g, A, geo);
+    }, dir == 0, full);
+  });
   return check_launch("sga column-block forward");
 }
 
@@ -275,7 +325,6 @@ int col_fwd(const float *x, const float *g, float *A, int S, int D, int H, int W
 // For inputs with few column blocks (SURVEY 8d's stress shape [1,1,192,240,624]: 39 blocks) and many disparities: 16 waves
 // per block instead of 4, 3-5 disparities of serial work per lane instead of 12-13, and -- unlike the register-only wide
 // segment kernels -- the same 64-byte global pieces as the 16-lane column blocks.  D <= 192; up to 112 KB of LDS per block.
-int device_cus();
 constexpr size_t COL_WIDE_SMEM_MAX = 152 * 1024;
 int col_wide_dpl(int D) { return D <= 64 * 3 ? 3 : 0; }      // (5 disparities per lane spill at the 128 registers a 1,024-thread block leaves)
 bool col_wide_ok(int D, int W, int dir, size_t smem, int S)
@@ -290,21 +339,16 @@ bool col_wide_ok(int D, int W, int dir, size_t smem, int S)
 
 int col_fwd_wide(const float *x, const float *g, float *A, int S, int D, int H, int W, int dir, hipStream_t st)
 {
-  ColGeom geo;
-  geo.D = D; geo.H = H; geo.W = W; geo.HW = (i64)H * W; geo.out_mode = 0; geo.tiled = 0;
+  const ColGeom geo = col_geom(D, H, W, 0, 0);
   const int dpl = col_wide_dpl(D);
   const bool full = D % dpl == 0;
   const size_t smem = col_smem_fwd(D);
   const dim3 grid((W + COL_NC - 1) / COL_NC, S), block(1024);
-#define X(P)                                                                                        \
-  if (dpl == (P)) {                                                                                 \
-    if (dir == 0 && full) GA_LAUNCH_SMEM_BIG((sga_col_fwd_wide<P, true, true>), grid, block, smem, st, x, g, A, geo);   \
-    else if (dir == 0) GA_LAUNCH_SMEM_BIG((sga_col_fwd_wide<P, true, false>), grid, block, smem, st, x, g, A, geo);     \
-    else if (full) GA_LAUNCH_SMEM_BIG((sga_col_fwd_wide<P, false, true>), grid, block, smem, st, x, g, A, geo);         \
-    else GA_LAUNCH_SMEM_BIG((sga_col_fwd_wide<P, false, false>), grid, block, smem, st, x, g, A, geo);                  \
-  }
-  X(3)
-#undef X
+  with_int<3>(dpl, [&](auto P) {
+    with_flags([&](auto asc, auto fl) {
+      GA_LAUNCH_SMEM_BIG((sga_col_fwd_wide<decltype(P)::value, decltype(asc)::value, decltype(fl)::value>), grid, block, smem, st, x, g, A, geo);
+    }, dir == 0, full);
+  });
   static const bool trace = getenv("GANET_TRACE_DISPATCH") != nullptr;
   if (trace) fprintf(stderr, "[ganet] sga_col_fwd_wide DPL=%d dir=%d D=%d smem=%zu\n", dpl, dir, D, smem);
   return check_launch("sga wide column-block forward");
@@ -313,21 +357,16 @@ int col_fwd_wide(const float *x, const float *g, float *A, int S, int D, int H, 
 int col_bwdg_wide(const float *g, const uint8_t *mask, const uint16_t *kp, const float *gout, float *G,
                   int S, int D, int H, int W, int dir, hipStream_t st)
 {
-  ColGeom geo;
-  geo.D = D; geo.H = H; geo.W = W; geo.HW = (i64)H * W; geo.out_mode = 0; geo.tiled = 0;
+  const ColGeom geo = col_geom(D, H, W, 0, 0);
   const int dpl = col_wide_dpl(D);
   const size_t smem = col_smem_bwdg(D);
   const dim3 grid((W + COL_NC - 1) / COL_NC, S), block(1024);
   const bool m16 = W % 16 == 0 && aligned16(mask);
-#define X(P)                                                                                        \
-  if (dpl == (P)) {                                                                                 \
-    if (dir == 1 && m16) GA_LAUNCH_SMEM_BIG((sga_col_bwdg_wide<P, true, true, false>), grid, block, smem, st, g, mask, kp, gout, G, geo, dir);  \
-    else if (dir == 1) GA_LAUNCH_SMEM_BIG((sga_col_bwdg_wide<P, true, false, false>), grid, block, smem, st, g, mask, kp, gout, G, geo, dir);   \
-    else if (m16) GA_LAUNCH_SMEM_BIG((sga_col_bwdg_wide<P, false, true, false>), grid, block, smem, st, g, mask, kp, gout, G, geo, dir);        \
-    else GA_LAUNCH_SMEM_BIG((sga_col_bwdg_wide<P, false, false, false>), grid, block, smem, st, g, mask, kp, gout, G, geo, dir);                \
-  }
-  X(3)
-#undef X
+  with_int<3>(dpl, [&](auto P) {
+    with_flags([&](auto asc, auto m) {
+      GA_LAUNCH_SMEM_BIG((sga_col_bwdg_wide<decltype(P)::value, decltype(asc)::value, decltype(m)::value, false>), grid, block, smem, st, g, mask, kp, gout, G, geo, dir);
+    }, dir == 1, m16);
+  });
   static const bool trace = getenv("GANET_TRACE_DISPATCH") != nullptr;
   if (trace) fprintf(stderr, "[ganet] sga_col_bwdg_wide DPL=%d dir=%d D=%d smem=%zu\n", dpl, dir, D, smem);
   return check_launch("sga wide column-block adjoint scan");
@@ -336,8 +375,7 @@ int col_bwdg_wide(const float *g, const uint8_t *mask, const uint16_t *kp, const
 int col_bwdg(const float *g, const uint8_t *mask, const uint16_t *kp, const float *gout, float *G,
              int S, int D, int H, int W, int dir, hipStream_t st, int tiled = 0)
 {
-  ColGeom geo;
-  geo.D = D; geo.H = H; geo.W = W; geo.HW = (i64)H * W; geo.out_mode = 0; geo.tiled = tiled;
+  const ColGeom geo = col_geom(D, H, W, 0, tiled);
   const int dpl = row_dpl(D);
   const size_t smem = col_smem_bwdg(D);
   const dim3 grid((W + COL_NC - 1) / COL_NC, S), block(256);
@@ -346,21 +384,12 @@ int col_bwdg(const float *g, const uint8_t *mask, const uint16_t *kp, const floa
   // (lanes wholly inside / outside [0, D): the leaner recurrence of bwdg_step<FULL>, instantiated for the depths the models use
   //  -- 33 and 48 at three, 65 at five disparities per lane)
   const bool full = D % dpl == 0;
-#define L(P, ASC, M, F) GA_LAUNCH_SMEM((sga_col_bwdg<P, ASC, M, F>), grid, block, smem, st, g, mask, kp, gout, G, geo, dir)
-#define X(P)                                                                                        \
-  if (dpl == (P)) {                                                                                 \
-    constexpr bool FL = (P) == 3 || (P) == 5;                                                       \
-    if (full && FL) {                                                                               \
-      if (dir == 1 && m16) L(P, true, true, FL); else if (dir == 1) L(P, true, false, FL);          \
-      else if (m16) L(P, false, true, FL); else L(P, false, false, FL);                             \
-    } else {                                                                                        \
-      if (dir == 1 && m16) L(P, true, true, false); else if (dir == 1) L(P, true, false, false);    \
-      else if (m16) L(P, false, true, false); else L(P, false, false, false);                       \
-    }                                                                                               \
-  }
-  GA_ROW_DPLS(X)
-#undef X
-#undef L
+  with_row_dpl(dpl, [&](auto P) {
+    with_flags([&](auto asc, auto m, auto fl) {
+      constexpr bool FL = decltype(fl)::value && (decltype(P)::value == 3 || decltype(P)::value == 5);
+      GA_LAUNCH_SMEM((sga_col_bwdg<decltype(P)::value, decltype(asc)::value, decltype(m)::value, FL>), grid, block, smem, st, g, mask, kp, gout, G, geo, dir);
+    }, dir == 1, m16, full);
+  });
   return check_launch("sga column-block adjoint scan");
 }
 
@@ -370,8 +399,6 @@ int row_bwdg(const float *g, const uint8_t *mask, const uint16_t *kp, const floa
   launch_row_bwdg(g, mask, kp, gout, G, S, D, H, W, dir, st);       // sga_row_tu.hip
   return check_launch("sga row adjoint scan");
 }
-
-int device_cus();
 
 // Inputs with few scanlines (a single slice at full resolution: SURVEY 8d's literal stress shape [1,1,192,240,624] has 624
 // columns / 240 rows) leave most of the 1,024 SIMDs without a wave when a scanline is 16 lanes wide (156 / 240 waves): the
@@ -389,97 +416,101 @@ bool few_lines(int N, int C, int D, int H, int W, int dir)
   return D >= 96 && lines * 16 < (i64)4 * device_cus() * 64 * 2;      // fewer 16-lane segments than two waves per SIMD hold
 }
 
+// ---- the one place that chooses the kernel family of an SGA scan ------------------------------------------------------------
+// In order of preference: wide column blocks, wide segments (GD = 64), row waves, column blocks, segments.
+enum ScanFamily { SCAN_COL_WIDE, SCAN_SEG_WIDE, SCAN_ROW_WAVE, SCAN_COL_BLOCK, SCAN_SEGMENT, SCAN_NONE };
+struct ScanQuery {
+  int N, C, D, H, W, dir;
+  bool adjoint;                         // the pass: forward scan | adjoint scan
+  bool vol16, mask4 = true, kp8 = true; // alignment facts: every volume 16 bytes, the mask 4, kp 8 (a forward scan has neither)
+};
+struct ScanChoice { ScanFamily family; int gd, dpl; };      // (gd, dpl): the segment kernels' pair
+
+// does this family's kernel apply to the scan?  (options, shape, LDS need and alignment; not: whether a better one does too)
+bool scan_family_ok(ScanFamily f, const ScanQuery &q)
+{
+  const int S = q.N * q.C, D = q.D;
+  switch (f) {
+    case SCAN_COL_WIDE: return col_wide_ok(D, q.W, q.dir, q.adjoint ? col_smem_bwdg(D) : col_smem_fwd(D), S) && q.vol16 && q.mask4;
+    case SCAN_SEG_WIDE: return few_lines(q.N, q.C, D, q.H, q.W, q.dir);
+    case SCAN_ROW_WAVE: return rowwave_ok(D, q.W, q.dir, q.adjoint ? row_smem_bwdg(D) : row_smem_fwd(D)) && q.vol16 && q.mask4 && q.kp8;
+    case SCAN_COL_BLOCK: return colblock_ok(D, q.W, q.dir, q.adjoint ? col_smem_bwdg(D) : col_smem_fwd(D)) && q.vol16 && q.mask4 && S <= 65535;
+    default: return f == SCAN_SEGMENT;
+  }
+}
+
+ScanChoice choose_scan(const ScanQuery &q)
+{
+  int gd = 0, dpl = 0;
+  if (scan_family_ok(SCAN_COL_WIDE, q)) return {SCAN_COL_WIDE, 0, 0};
+  if (scan_family_ok(SCAN_SEG_WIDE, q) && pick_pair(q.D, 64, &gd, &dpl)) return {SCAN_SEGMENT, gd, dpl};
+  if (scan_family_ok(SCAN_ROW_WAVE, q)) return {SCAN_ROW_WAVE, 0, 0};
+  if (scan_family_ok(SCAN_COL_BLOCK, q)) return {SCAN_COL_BLOCK, 0, 0};
+  if (!pick_pair(q.D, 16, &gd, &dpl)) return {SCAN_NONE, 0, 0};
+  return {SCAN_SEGMENT, gd, dpl};
+}
+
+int no_scan_kernel(const ScanChoice &c, int D)
+{
+  if (c.family == SCAN_NONE) return fail(GANET_E_UNSUPPORTED, "SGA: D=%d exceeds the compiled maximum (1088)", D);
+  return fail(GANET_E_UNSUPPORTED, "SGA: no kernel for GD=%d DPL=%d", c.gd, c.dpl);
+}
+
 // 1 if ganet_sga_backward keeps G_down / G_up in the tiled layout of sga_col_kernels.h for these dimensions: where the 16-lane
-// column-block adjoint kernel runs (not the wide one), W % 16 == 0, H % 4 == 0.  Decided from the dimensions and GANET_SGA_TILED.
-int sga_ws_tiled(int N, int C, int D, int H, int W)
+// column-block adjoint kernel runs (not the wide one), W % 16 == 0, H % 4 == 0.  Decided from the dimensions and GANET_SGA_TILED,
+// and from the alignment of what the tiled column kernels touch where the caller knows it.
+int sga_ws_tiled(int N, int C, int D, int H, int W, bool vol16 = true, bool mask4 = true)
 {
   if (!opts().sga_tiled || W % 16 != 0 || H % 4 != 0 || N * C > 65535 || opts().wide_scan == 2) return 0;
-  return (!col_wide_ok(D, W, 0, col_smem_bwdg(D), N * C) && colblock_ok(D, W, 0, col_smem_bwdg(D))) ? 1 : 0;
+  const ScanQuery q = {N, C, D, H, W, 0, true, vol16, mask4};
+  return (!scan_family_ok(SCAN_COL_WIDE, q) && scan_family_ok(SCAN_COL_BLOCK, q)) ? 1 : 0;
 }
 
 int scan_fwd(const float *x, const float *g, float *A, int N, int C, int D, int H, int W, int dir,
              hipStream_t st)
 {
-  if (col_wide_ok(D, W, dir, col_smem_fwd(D), N * C) && aligned16(x) && aligned16(g) && aligned16(A))
-    return col_fwd_wide(x, g, A, N * C, D, H, W, dir, st);
-  if (few_lines(N, C, D, H, W, dir)) {
-    int gd, dpl;
-    if (pick_pair(D, 64, &gd, &dpl)) {
-#define X(G, P) \
-      if ((G) == 64 && dpl == (P)) return launch_scan_fwd<G, P>(x, g, A, N * C, D, H, W, dir, st);
-      GA_SGA_PAIRS(X)
-#undef X
-    }
-  }
-  if (rowwave_ok(D, W, dir, row_smem_fwd(D)) && aligned16(x) && aligned16(g) && aligned16(A))
-    return row_fwd(x, g, A, N * C, D, H, W, dir, st);
-  if (colblock_ok(D, W, dir, col_smem_fwd(D)) && aligned16(x) && aligned16(g) && aligned16(A) && N * C <= 65535)
-    return col_fwd(x, g, A, N * C, D, H, W, dir, st);
-  int gd, dpl;
-  if (!pick_pair(D, 16, &gd, &dpl))
-    return fail(GANET_E_UNSUPPORTED, "SGA: D=%d exceeds the compiled maximum (1088)", D);
-#define X(G, P) \
-  if (gd == (G) && dpl == (P)) return launch_scan_fwd<G, P>(x, g, A, N * C, D, H, W, dir, st);
-  GA_SGA_PAIRS(X)
-#undef X
-  return fail(GANET_E_UNSUPPORTED, "SGA: no kernel for GD=%d DPL=%d", gd, dpl);
+  const ScanChoice c = choose_scan({N, C, D, H, W, dir, false, aligned16(x, g, A)});
+  if (c.family == SCAN_COL_WIDE) return col_fwd_wide(x, g, A, N * C, D, H, W, dir, st);
+  if (c.family == SCAN_ROW_WAVE) return row_fwd(x, g, A, N * C, D, H, W, dir, st);
+  if (c.family == SCAN_COL_BLOCK) return col_fwd(x, g, A, N * C, D, H, W, dir, st);
+  int rc;
+  if (with_sga_pair(c.gd, c.dpl, [&](auto G, auto P) {
+        rc = launch_scan_fwd<decltype(G)::value, decltype(P)::value>(x, g, A, N * C, D, H, W, dir, st);
+      }))
+    return rc;
+  return no_scan_kernel(c, D);
 }
 
 int scan_bwdg(const float *g, const uint8_t *mask, const uint16_t *kp, const float *gout, float *G,
               int N, int C, int D, int H, int W, int dir, hipStream_t st, int tiled = 0)
 {
+  const bool vol16 = aligned16(g, gout, G);
   if (tiled) {
-    if (!(aligned16(g) && aligned16(gout) && aligned16(G) && (((uintptr_t)mask & 3) == 0)))
-      return fail(GANET_E_UNSUPPORTED, "SGA: tiled workspace needs 16-byte aligned volumes");
+    if (!(vol16 && aligned4(mask))) return fail(GANET_E_UNSUPPORTED, "SGA: tiled workspace needs 16-byte aligned volumes");
     return col_bwdg(g, mask, kp, gout, G, N * C, D, H, W, dir, st, 1);
   }
-  if (col_wide_ok(D, W, dir, col_smem_bwdg(D), N * C) && aligned16(g) && aligned16(gout) && aligned16(G) &&
-      (((uintptr_t)mask & 3) == 0))
-    return col_bwdg_wide(g, mask, kp, gout, G, N * C, D, H, W, dir, st);
-  if (few_lines(N, C, D, H, W, dir)) {
-    int gd, dpl;
-    if (pick_pair(D, 64, &gd, &dpl)) {
-#define X(G_, P) \
-      if ((G_) == 64 && dpl == (P)) return launch_scan_bwdg<G_, P>(g, mask, kp, gout, G, N * C, D, H, W, dir, st);
-      GA_SGA_PAIRS(X)
-#undef X
-    }
-  }
-  if (rowwave_ok(D, W, dir, row_smem_bwdg(D)) && aligned16(g) && aligned16(gout) && aligned16(G) &&
-      (((uintptr_t)mask & 3) == 0) && (((uintptr_t)kp & 7) == 0))
-    return row_bwdg(g, mask, kp, gout, G, N * C, D, H, W, dir, st);
-  if (colblock_ok(D, W, dir, col_smem_bwdg(D)) && aligned16(g) && aligned16(gout) && aligned16(G) &&
-      (((uintptr_t)mask & 3) == 0) && N * C <= 65535)
-    return col_bwdg(g, mask, kp, gout, G, N * C, D, H, W, dir, st);
-  int gd, dpl;
-  if (!pick_pair(D, 16, &gd, &dpl))
-    return fail(GANET_E_UNSUPPORTED, "SGA: D=%d exceeds the compiled maximum (1088)", D);
-#define X(G_, P) \
-  if (gd == (G_) && dpl == (P)) return launch_scan_bwdg<G_, P>(g, mask, kp, gout, G, N * C, D, H, W, dir, st);
-  GA_SGA_PAIRS(X)
-#undef X
-  return fail(GANET_E_UNSUPPORTED, "SGA: no kernel for GD=%d DPL=%d", gd, dpl);
+  const ScanChoice c = choose_scan({N, C, D, H, W, dir, true, vol16, aligned4(mask), aligned8(kp)});
+  if (c.family == SCAN_COL_WIDE) return col_bwdg_wide(g, mask, kp, gout, G, N * C, D, H, W, dir, st);
+  if (c.family == SCAN_ROW_WAVE) return row_bwdg(g, mask, kp, gout, G, N * C, D, H, W, dir, st);
+  if (c.family == SCAN_COL_BLOCK) return col_bwdg(g, mask, kp, gout, G, N * C, D, H, W, dir, st);
+  int rc;
+  if (with_sga_pair(c.gd, c.dpl, [&](auto GD, auto P) {
+        rc = launch_scan_bwdg<decltype(GD)::value, decltype(P)::value>(g, mask, kp, gout, G, N * C, D, H, W, dir, st);
+      }))
+    return rc;
+  return no_scan_kernel(c, D);
 }
 
 int scan_bwdg_f32mask(const float *g, const float *mask, const uint16_t *kp, const float *gout, float *G,
                       int N, int C, int D, int H, int W, int dir, hipStream_t st)
 {
-  int gd, dpl;
-  if (!pick_pair(D, 16, &gd, &dpl))
-    return fail(GANET_E_UNSUPPORTED, "SGA: D=%d exceeds the compiled maximum (1088)", D);
-#define X(G_, P) \
-  if (((G_) == 16 || (G_) == 64) && gd == (G_) && dpl == (P)) return launch_scan_bwdg_f32mask<G_, P>(g, mask, kp, gout, G, N * C, D, H, W, dir, st);
-  GA_SGA_PAIRS(X)
-#undef X
+  int gd, dpl, rc;
+  if (!pick_pair(D, 16, &gd, &dpl)) return fail(GANET_E_UNSUPPORTED, "SGA: D=%d exceeds the compiled maximum (1088)", D);
+  if (with_sga_pair(gd, dpl, [&](auto GD, auto P) {
+        rc = launch_scan_bwdg_f32mask<decltype(GD)::value, decltype(P)::value>(g, mask, kp, gout, G, N * C, D, H, W, dir, st);
+      }))
+    return rc;
   return fail(GANET_E_UNSUPPORTED, "SGA: no kernel for DPL=%d", dpl);
-}
-
-int px_grid(i64 npix)
-{
-  i64 g = (npix + 255) / 256;
-  if (g > 256 * 32) g = 256 * 32;
-  if (g < 1) g = 1;
-  return (int)g;
 }
 
 // per-pixel gradients for `ndir` (1 or 4) directions
@@ -488,24 +519,15 @@ int bwd_point(const float *x, float *gx, const PointArgs &pa, int ndir, int N, i
 {
   const i64 npix = (i64)N * C * H * W;
   const int pb = 256;      // (64 / 128 measured equal)
-  i64 gsz = (npix + pb - 1) / pb;
-  const i64 gmax = (i64)256 * 32 * (256 / pb);
-  if (gsz > gmax) gsz = gmax;
-  if (gsz < 1) gsz = 1;
-  if (ndir == 4 && !accumulate && tiled) GA_LAUNCH((sga_bwd_point<4, false, true>), dim3((unsigned)gsz), dim3(pb), st, x, gx, pa, D, H, W, npix);
-  else if (ndir == 4 && accumulate) GA_LAUNCH((sga_bwd_point<4, true>), dim3((unsigned)gsz), dim3(pb), st, x, gx, pa, D, H, W, npix);
-  else if (ndir == 4) GA_LAUNCH((sga_bwd_point<4, false>), dim3((unsigned)gsz), dim3(pb), st, x, gx, pa, D, H, W, npix);
-  else if (accumulate) GA_LAUNCH((sga_bwd_point<1, true>), dim3((unsigned)gsz), dim3(pb), st, x, gx, pa, D, H, W, npix);
-  else GA_LAUNCH((sga_bwd_point<1, false>), dim3((unsigned)gsz), dim3(pb), st, x, gx, pa, D, H, W, npix);
+  const dim3 grid(clamp_grid(npix, pb, (i64)256 * 32 * (256 / pb)));
+  // (the tiled layout of G_down / G_up is compiled for the four-direction, non-accumulating form alone: sga_bwd_point<4, false, true>)
+  with_flags([&](auto four, auto acc, auto til) {
+    constexpr int ND = decltype(four)::value ? 4 : 1;
+    constexpr bool ACC = decltype(acc)::value, TG = decltype(til)::value;
+    if constexpr (!TG || (ND == 4 && !ACC))
+      GA_LAUNCH((sga_bwd_point<ND, ACC, TG>), grid, dim3(pb), st, x, gx, pa, D, H, W, npix);
+  }, ndir == 4, accumulate != 0, ndir == 4 && !accumulate && tiled);
   return check_launch("sga per-pixel gradients");
-}
-
-int ew_grid(i64 n)
-{
-  i64 g = (n + 255) / 256;
-  if (g > 256 * 16) g = 256 * 16;
-  if (g < 1) g = 1;
-  return (int)g;
 }
 
 // compute units of the current device (256 on MI355X); the emulator build reports 256
@@ -584,37 +606,52 @@ LgaSegMix lga_items(int W, int H, int B, int D, bool whole_only, i64 *items, boo
 #endif
 #define GA_LGA_PLANAR 1     // API-layout operands of the plane-pair kernels staged planar by 16-byte copies where W % 4 == 0
 #endif
+// API-layout operand of the plane-pair kernels staged planar by 16-byte copies (radius 2 alone)
+template <int R> bool lga_planar(int W, const float *x) { return R == 2 && GA_LGA_PLANAR && W % 4 == 0 && aligned16(x); }
+
+LgaGeom lga_geom(int D, int H, int W)
+{
+  LgaGeom geo;
+  geo.D = D; geo.H = H; geo.W = W; geo.HW = (i64)H * W;
+  return geo;
+}
+
+// the items of a pass that takes whole 32 x 2 tiles, one depth segment each
+LgaSeg lga_whole_tiles(int W, int H, int B, int D, i64 *items)
+{
+  LgaSeg sg;
+  sg.tiles_x = (W + LGA_TW - 1) / LGA_TW;
+  sg.tiles_y = (H + LGAW_TH - 1) / LGAW_TH;
+  sg.nseg = 1; sg.seg_len = D;
+  *items = (i64)sg.tiles_x * sg.tiles_y * B;
+  return sg;
+}
+
 template <int R>
 int launch_lga_fwd(const float *x, const float *f, float *y, int B, int D, int H, int W,
                    bool transposed, hipStream_t st)
 {
-  LgaGeom geo;
-  geo.D = D; geo.H = H; geo.W = W; geo.HW = (i64)H * W;
+  const LgaGeom geo = lga_geom(D, H, W);
   if constexpr (R <= 2) {
     const int family = opts().lga_wave;
     if (family && (i64)H * W < (1ll << 28)) {
       i64 items;
-      bool planar = false;
-      if constexpr (R == 2) planar = GA_LGA_PLANAR && W % 4 == 0 && aligned16(x);      // input staged by 16-byte copies
+      const bool planar = lga_planar<R>(W, x);
       if constexpr (R == 2) {
         if (planar && family == 2) {                      // one ring per 256-thread workgroup (32 x 8 tiles)
           const LgaSegMix wx = lga_items(W, H, B, D, false, &items, true);
           if (items < (1ll << 31)) {
-            if (transposed) GA_LAUNCH((lga_apply_pp_wx<2, true>), dim3((unsigned)items), dim3(256), st, x, f, y, geo, wx);
-            else GA_LAUNCH((lga_apply_pp_wx<2, false>), dim3((unsigned)items), dim3(256), st, x, f, y, geo, wx);
+            with_flags([&](auto t) { GA_LAUNCH((lga_apply_pp_wx<2, decltype(t)::value>), dim3((unsigned)items), dim3(256), st, x, f, y, geo, wx); }, transposed);
             return check_launch("lga apply (plane pairs, workgroup ring)");
           }
         }
       }
       const LgaSegMix mx = lga_items(W, H, B, D, false, &items);
       if (items < (1ll << 31)) {
-        if constexpr (R == 2) {
-          if (planar && transposed) GA_LAUNCH((lga_apply_pp_x<2, true>), dim3((unsigned)items), dim3(64), st, x, f, y, geo, mx);
-          else if (planar) GA_LAUNCH((lga_apply_pp_x<2, false>), dim3((unsigned)items), dim3(64), st, x, f, y, geo, mx);
-        }
-        if (planar) {}
-        else if (transposed) GA_LAUNCH((lga_apply_pp<R, true>), dim3((unsigned)items), dim3(64), st, x, f, y, geo, mx);
-        else GA_LAUNCH((lga_apply_pp<R, false>), dim3((unsigned)items), dim3(64), st, x, f, y, geo, mx);
+        with_flags([&](auto t, auto pl) {      // (planar: R == 2 alone)
+          if constexpr (!decltype(pl)::value) GA_LAUNCH((lga_apply_pp<R, decltype(t)::value>), dim3((unsigned)items), dim3(64), st, x, f, y, geo, mx);
+          else if constexpr (R == 2) GA_LAUNCH((lga_apply_pp_x<2, decltype(t)::value>), dim3((unsigned)items), dim3(64), st, x, f, y, geo, mx);
+        }, transposed, planar);
         static const bool trace = getenv("GANET_TRACE_DISPATCH") != nullptr;      // (development: which LGA kernel ran)
         if (trace) fprintf(stderr, "[ganet] lga_apply_pp R=%d T=%d items=%lld: %d whole tiles + segments of %d planes x %d\n", R, (int)transposed, (long long)items, mx.n_whole, mx.sub_len, mx.nsub);
         return check_launch("lga apply (plane pairs)");
@@ -622,8 +659,7 @@ int launch_lga_fwd(const float *x, const float *f, float *y, int B, int D, int H
     }
   }
   const dim3 grid((W + LGA_TW - 1) / LGA_TW, (H + LGA_TH - 1) / LGA_TH, B);
-  if (transposed) GA_LAUNCH((lga_apply<R, true>), grid, dim3(LGA_NT), st, x, f, y, geo);
-  else GA_LAUNCH((lga_apply<R, false>), grid, dim3(LGA_NT), st, x, f, y, geo);
+  with_flags([&](auto t) { GA_LAUNCH((lga_apply<R, decltype(t)::value>), grid, dim3(LGA_NT), st, x, f, y, geo); }, transposed);
   return check_launch("lga apply");
 }
 
@@ -633,38 +669,33 @@ int launch_lga_paired(const float *x, const float *f, float *y, int B, int D, in
 {
   if ((i64)H * W >= (1ll << 28) || W % 2 != 0 || !aligned16(x) || !aligned16(y))
     return fail(GANET_E_UNSUPPORTED, "ganet_lga_apply_paired: needs W even, planes below 2^28 pixels and 16-byte aligned volumes");
-  LgaGeom geo;
-  geo.D = D; geo.H = H; geo.W = W; geo.HW = (i64)H * W;
+  const LgaGeom geo = lga_geom(D, H, W);
   i64 items;
   float *const none = nullptr;
   const bool wg_ring = opts().lga_wave == 2;
-  if (x_paired && wg_ring) {                                       // one ring per 256-thread workgroup (32 x 8 tiles)
+  const bool planar = GA_LGA_PLANAR && W % 4 == 0;      // API-layout input staged planar, two 16-byte copies per plane pair
+  if (wg_ring && (x_paired || planar)) {                // one ring per 256-thread workgroup (32 x 8 tiles)
     const LgaSegMix wx = lga_items(W, H, B, D, false, &items, true);
     if (items < (1ll << 31)) {
-      if (transposed) GA_LAUNCH((lga_apply_pp_wpi<2, true>), dim3((unsigned)items), dim3(256), st, x, f, y, geo, wx, none, none, edge);
-      else GA_LAUNCH((lga_apply_pp_wpi<2, false>), dim3((unsigned)items), dim3(256), st, x, f, y, geo, wx, none, none, edge);
-      return check_launch("lga apply (plane pairs, interleaved input, workgroup ring)");
-    }
-  }
-  if (!x_paired && GA_LGA_PLANAR && W % 4 == 0 && wg_ring) {      // one ring per 256-thread workgroup (32 x 8 tiles)
-    const LgaSegMix wx = lga_items(W, H, B, D, false, &items, true);
-    if (items < (1ll << 31)) {
-      if (transposed) GA_LAUNCH((lga_apply_pp_wxo<2, true>), dim3((unsigned)items), dim3(256), st, x, f, y, geo, wx, none, none, edge);
-      else GA_LAUNCH((lga_apply_pp_wxo<2, false>), dim3((unsigned)items), dim3(256), st, x, f, y, geo, wx, none, none, edge);
-      return check_launch("lga apply (plane pairs, interleaved volume, workgroup ring)");
+      const dim3 grid((unsigned)items), block(256);
+      with_flags([&](auto t, auto xp) {
+        constexpr bool T = decltype(t)::value;
+        if constexpr (decltype(xp)::value) GA_LAUNCH((lga_apply_pp_wpi<2, T>), grid, block, st, x, f, y, geo, wx, none, none, edge);
+        else GA_LAUNCH((lga_apply_pp_wxo<2, T>), grid, block, st, x, f, y, geo, wx, none, none, edge);
+      }, transposed, x_paired);
+      return check_launch(x_paired ? "lga apply (plane pairs, interleaved input, workgroup ring)"
+                                   : "lga apply (plane pairs, interleaved volume, workgroup ring)");
     }
   }
   const LgaSegMix sg = lga_items(W, H, B, D, false, &items);
   if (items >= (1ll << 31)) return fail(GANET_E_UNSUPPORTED, "ganet_lga_apply_paired: too many tiles");
-#define L(K, T) GA_LAUNCH((K<2, T>), dim3((unsigned)items), dim3(64), st, x, f, y, geo, sg, none, none, edge)
-  if (x_paired) {
-    if (transposed) L(lga_apply_pp_pi, true); else L(lga_apply_pp_pi, false);
-  } else if (GA_LGA_PLANAR && W % 4 == 0) {      // API-layout input staged planar, two 16-byte copies per plane pair
-    if (transposed) L(lga_apply_pp_xo, true); else L(lga_apply_pp_xo, false);
-  } else {
-    if (transposed) L(lga_apply_pp_po, true); else L(lga_apply_pp_po, false);
-  }
-#undef L
+  const dim3 grid((unsigned)items), block(64);
+  with_flags([&](auto t, auto xp, auto pl) {
+    constexpr bool T = decltype(t)::value;
+    if constexpr (decltype(xp)::value) GA_LAUNCH((lga_apply_pp_pi<2, T>), grid, block, st, x, f, y, geo, sg, none, none, edge);
+    else if constexpr (decltype(pl)::value) GA_LAUNCH((lga_apply_pp_xo<2, T>), grid, block, st, x, f, y, geo, sg, none, none, edge);
+    else GA_LAUNCH((lga_apply_pp_po<2, T>), grid, block, st, x, f, y, geo, sg, none, none, edge);
+  }, transposed, x_paired, planar);
   return check_launch("lga apply (plane pairs, interleaved volume)");
 }
 
@@ -673,13 +704,9 @@ int launch_lga_gf_paired(const float *x, const float *gy, float *gf, int B, int 
 {
   if ((i64)H * W >= (1ll << 28) || W % 2 != 0 || !aligned16(x) || !aligned16(gy))
     return fail(GANET_E_UNSUPPORTED, "ganet_lga_filter_grad_paired: needs W even, planes below 2^28 pixels and 16-byte aligned volumes");
-  LgaGeom geo;
-  geo.D = D; geo.H = H; geo.W = W; geo.HW = (i64)H * W;
-  LgaSeg sg;
-  sg.tiles_x = (W + LGA_TW - 1) / LGA_TW;
-  sg.tiles_y = (H + LGAW_TH - 1) / LGAW_TH;
-  sg.nseg = 1; sg.seg_len = D;
-  const i64 items = (i64)sg.tiles_x * sg.tiles_y * B;
+  const LgaGeom geo = lga_geom(D, H, W);
+  i64 items;
+  const LgaSeg sg = lga_whole_tiles(W, H, B, D, &items);
   if (items >= (1ll << 31)) return fail(GANET_E_UNSUPPORTED, "ganet_lga_filter_grad_paired: too many tiles");
   const bool fg_pair = GA_FGP_DEFAULT && opts().lga_wave >= 2;      // the workgroup forms: here the taps of a tile split over a wave pair (lga_filter_grad_pair.inc)
   if (x_paired && fg_pair) GA_LAUNCH((lga_filter_grad_pair_xp<GA_FGP_WPS>), dim3((unsigned)items), dim3(128), st, x, gy, gf, geo, sg, acc);
@@ -696,17 +723,14 @@ int launch_lga_fwd_regress(const float *x, const float *f, float *y, float *snor
 {
   if constexpr (R <= 2) {
     if ((i64)H * W < (1ll << 28)) {
-      LgaGeom geo;
-      geo.D = D; geo.H = H; geo.W = W; geo.HW = (i64)H * W;
+      const LgaGeom geo = lga_geom(D, H, W);
       i64 items;
       const LgaSegMix sg = lga_items(W, H, B, D, true, &items);      // (the epilogue reduces over all of D: whole tiles only)
       if (items < (1ll << 31)) {
-        bool planar = false;
-        if constexpr (R == 2) {
-          planar = GA_LGA_PLANAR && W % 4 == 0 && aligned16(x);
-          if (planar) GA_LAUNCH((lga_apply_pp_x<2, false, true>), dim3((unsigned)items), dim3(64), st, x, f, y, geo, sg, snorm, sdy);
-        }
-        if (!planar) GA_LAUNCH((lga_apply_pp<R, false, true>), dim3((unsigned)items), dim3(64), st, x, f, y, geo, sg, snorm, sdy);
+        with_flags([&](auto pl) {
+          if constexpr (!decltype(pl)::value) GA_LAUNCH((lga_apply_pp<R, false, true>), dim3((unsigned)items), dim3(64), st, x, f, y, geo, sg, snorm, sdy);
+          else if constexpr (R == 2) GA_LAUNCH((lga_apply_pp_x<2, false, true>), dim3((unsigned)items), dim3(64), st, x, f, y, geo, sg, snorm, sdy);
+        }, lga_planar<R>(W, x));
         return check_launch("lga apply + regression epilogue (plane pairs)");
       }
     }
@@ -719,22 +743,16 @@ template <int R>
 int launch_lga_gf(const float *x, const float *gy, float *gf, int B, int D, int H, int W, int acc,
                   hipStream_t st)
 {
-  LgaGeom geo;
-  geo.D = D; geo.H = H; geo.W = W; geo.HW = (i64)H * W;
+  const LgaGeom geo = lga_geom(D, H, W);
   if constexpr (R <= 2) {
     if (opts().lga_wave && (i64)H * W < (1ll << 28)) {
-      LgaSeg sg;
-      sg.tiles_x = (W + LGA_TW - 1) / LGA_TW;
-      sg.tiles_y = (H + LGAW_TH - 1) / LGAW_TH;
-      sg.nseg = 1; sg.seg_len = D;
-      const i64 items = (i64)sg.tiles_x * sg.tiles_y * B;
+      i64 items;
+      const LgaSeg sg = lga_whole_tiles(W, H, B, D, &items);
       if (items < (1ll << 31)) {
-        bool planar = false;
-        if constexpr (R == 2) {
-          planar = GA_LGA_PLANAR && W % 4 == 0 && aligned16(x);
-          if (planar) GA_LAUNCH((lga_filter_grad_pp_x<2, 3, 0>), dim3((unsigned)items), dim3(64), st, x, gy, gf, geo, sg, acc);
-        }
-        if (!planar) GA_LAUNCH((lga_filter_grad_pp<R, 3, 0>), dim3((unsigned)items), dim3(64), st, x, gy, gf, geo, sg, acc);
+        with_flags([&](auto pl) {
+          if constexpr (!decltype(pl)::value) GA_LAUNCH((lga_filter_grad_pp<R, 3, 0>), dim3((unsigned)items), dim3(64), st, x, gy, gf, geo, sg, acc);
+          else if constexpr (R == 2) GA_LAUNCH((lga_filter_grad_pp_x<2, 3, 0>), dim3((unsigned)items), dim3(64), st, x, gy, gf, geo, sg, acc);
+        }, lga_planar<R>(W, x));
         return check_launch("lga filter grad (plane pairs)");
       }
     }
@@ -746,10 +764,8 @@ int launch_lga_gf(const float *x, const float *gy, float *gf, int B, int D, int 
 
 int check_lga(const char *who, int B, int D, int H, int W, int radius)
 {
-  if (B <= 0 || D <= 0 || H <= 0 || W <= 0)
-    return fail(GANET_E_INVALID, "%s: non-positive size B=%d D=%d H=%d W=%d", who, B, D, H, W);
-  if (radius < 1 || radius > 3)
-    return fail(GANET_E_UNSUPPORTED, "%s: radius %d not in the compiled set {1,2,3}", who, radius);
+  if (B <= 0 || D <= 0 || H <= 0 || W <= 0) return fail(GANET_E_INVALID, "%s: non-positive size B=%d D=%d H=%d W=%d", who, B, D, H, W);
+  if (radius < 1 || radius > 3) return fail(GANET_E_UNSUPPORTED, "%s: radius %d not in the compiled set {1,2,3}", who, radius);
   if (B > 65535) return fail(GANET_E_UNSUPPORTED, "%s: batch %d > 65535 (grid.z)", who, B);
   return GANET_OK;
 }
@@ -796,23 +812,18 @@ GA_EXPORT int ganet_is_simulator(void)
 
 GA_EXPORT int ganet_get_option(const char *name)
 {
+  const char *who = "ganet_get_option";
   opts();
-  if (!name) return fail(GANET_E_INVALID, "ganet_get_option: null name");
-  if (!strcmp(name, "GANET_LGA_WAVE")) return g_opt.lga_wave;
-  if (!strcmp(name, "GANET_SGA_TILED")) return g_opt.sga_tiled;
-  if (!strcmp(name, "GANET_LGA_MIX")) return g_opt.lga_mix;
-  if (!strcmp(name, "GANET_LGA_SEGS")) return g_opt.lga_segs;
-  if (!strcmp(name, "GANET_SGA_WIDE_SCAN")) return g_opt.wide_scan;
-  if (!strcmp(name, "GANET_SGA_WIDE_COL")) return g_opt.wide_col;
-  if (!strcmp(name, "GANET_SGA_ROWWAVE")) return g_opt.rowwave;
-  if (!strcmp(name, "GANET_SGA_COLBLOCK")) return g_opt.colblock;
-  return fail(GANET_E_INVALID, "ganet_get_option: unknown option %s", name);
+  if (!name) return fail(GANET_E_INVALID, "%s: null name", who);
+  if (const OptionDesc *o = find_option(name)) return g_opt.*o->field;
+  return fail(GANET_E_INVALID, "%s: unknown option %s", who, name);
 }
 
 GA_EXPORT int ganet_set_option(const char *name, int value)
 {
+  const char *who = "ganet_set_option";
   opts();
-  if (!name) return fail(GANET_E_INVALID, "ganet_set_option: null name");
+  if (!name) return fail(GANET_E_INVALID, "%s: null name", who);
   if (store_option(name, value)) {}      // a library option, normalised
 #if defined(GA_HIPSIM)
   else if (!strcmp(name, "HIPSIM_LATE_DMA")) hipsim::S().late_dma = value != 0;   // emulator only: see tests/hipsim/hipsim.h
@@ -836,7 +847,7 @@ GA_EXPORT int ganet_set_option(const char *name, int value)
         if (!noted.exchange(1)) fprintf(stderr, "[ganet] ganet_set_option: %s is retired (no effect); see INTEGRATION.md\n", name);
         return GANET_OK;
       }
-    return fail(GANET_E_INVALID, "ganet_set_option: unknown option %s", name);
+    return fail(GANET_E_INVALID, "%s: unknown option %s", who, name);
   }
   return GANET_OK;
 }
@@ -844,18 +855,20 @@ GA_EXPORT int ganet_set_option(const char *name, int value)
 GA_EXPORT int ganet_sga_scan_forward(const float *x, const float *g, float *A, int N, int C, int D,
                                      int H, int W, int dir, void *stream)
 {
-  if (!x || !g || !A) return fail(GANET_E_INVALID, "ganet_sga_scan_forward: null pointer");
-  if (dir < 0 || dir > 3) return fail(GANET_E_INVALID, "ganet_sga_scan_forward: dir %d", dir);
-  GA_TRY(check_dims5("ganet_sga_scan_forward", N, C, D, H, W));
+  const char *who = "ganet_sga_scan_forward";
+  GA_TRY(check_ptrs(who, x, g, A));
+  GA_TRY(check_dir(who, dir));
+  GA_TRY(check_dims5(who, N, C, D, H, W));
   return scan_fwd(x, g, A, N, C, D, H, W, dir, (hipStream_t)stream);
 }
 
 GA_EXPORT int ganet_sga_scan_forward_ws(const float *x, const float *g, float *A_ws, int N, int C, int D, int H, int W, int dir,
                                          void *stream)
 {
-  if (!x || !g || !A_ws) return fail(GANET_E_INVALID, "ganet_sga_scan_forward_ws: null pointer");
-  if (dir < 0 || dir > 3) return fail(GANET_E_INVALID, "ganet_sga_scan_forward_ws: dir %d", dir);
-  GA_TRY(check_dims5("ganet_sga_scan_forward_ws", N, C, D, H, W));
+  const char *who = "ganet_sga_scan_forward_ws";
+  GA_TRY(check_ptrs(who, x, g, A_ws));
+  GA_TRY(check_dir(who, dir));
+  GA_TRY(check_dims5(who, N, C, D, H, W));
   const i64 n = (i64)N * C * D * H * W;
   return scan_fwd(x, g, A_ws + dir * n, N, C, D, H, W, dir, (hipStream_t)stream);
 }
@@ -863,9 +876,10 @@ GA_EXPORT int ganet_sga_scan_forward_ws(const float *x, const float *g, float *A
 GA_EXPORT int ganet_sga_backward_scan_ws(const float *g, const uint8_t *mask, const uint16_t *kp, const float *grad_out, float *G_ws,
                                           int N, int C, int D, int H, int W, int dir, void *stream)
 {
-  if (!g || !mask || !kp || !grad_out || !G_ws) return fail(GANET_E_INVALID, "ganet_sga_backward_scan_ws: null pointer");
-  if (dir < 0 || dir > 3) return fail(GANET_E_INVALID, "ganet_sga_backward_scan_ws: dir %d", dir);
-  GA_TRY(check_dims5("ganet_sga_backward_scan_ws", N, C, D, H, W));
+  const char *who = "ganet_sga_backward_scan_ws";
+  GA_TRY(check_ptrs(who, g, mask, kp, grad_out, G_ws));
+  GA_TRY(check_dir(who, dir));
+  GA_TRY(check_dims5(who, N, C, D, H, W));
   const i64 n = (i64)N * C * D * H * W, npix = (i64)N * C * H * W;
   return scan_bwdg(g, mask, kp + dir * npix, grad_out, G_ws + dir * n, N, C, D, H, W, dir, (hipStream_t)stream,
                    dir < 2 && sga_ws_tiled(N, C, D, H, W));
@@ -880,14 +894,15 @@ GA_EXPORT int ganet_sga_workspace_layout(int N, int C, int D, int H, int W)
 GA_EXPORT int ganet_sga_merge(const float *A_ws, float *out, uint8_t *mask, uint16_t *kp, int N, int C, int D, int H, int W,
                                void *stream)
 {
-  if (!A_ws || !out || !mask || !kp) return fail(GANET_E_INVALID, "ganet_sga_merge: null pointer");
-  GA_TRY(check_dims5("ganet_sga_merge", N, C, D, H, W));
-  if (D > 65535) return fail(GANET_E_UNSUPPORTED, "ganet_sga_merge: D > 65535");
+  const char *who = "ganet_sga_merge";
+  GA_TRY(check_ptrs(who, A_ws, out, mask, kp));
+  GA_TRY(check_dims5(who, N, C, D, H, W));
+  if (D > 65535) return fail(GANET_E_UNSUPPORTED, "%s: D > 65535", who);
   const i64 n = (i64)N * C * D * H * W;
   const i64 npix = (i64)N * C * H * W;
   hipStream_t st = (hipStream_t)stream;
   const i64 HWl = (i64)H * W;
-  const bool al = aligned16(A_ws) && aligned16(out) && (((uintptr_t)mask & 3) == 0) && (((uintptr_t)kp & 7) == 0);
+  const bool al = aligned16(A_ws, out) && aligned4(mask) && aligned8(kp);
   if (HWl % 4 == 0 && al && npix / 4 / 64 + 1 < (1ll << 31)) {
     GA_LAUNCH(sga_merge_px4, dim3((unsigned)((npix / 4 + 63) / 64)), dim3(64), st, A_ws, A_ws + n, A_ws + 2 * n,
               A_ws + 3 * n, out, mask, kp, D, HWl, npix);
@@ -902,10 +917,10 @@ GA_EXPORT int ganet_sga_forward(const float *x, const float *g0, const float *g1
                                 const float *g3, float *A_ws, float *out, uint8_t *mask,
                                 uint16_t *kp, int N, int C, int D, int H, int W, void *stream)
 {
-  if (!x || !g0 || !g1 || !g2 || !g3 || !A_ws || !out || !mask || !kp)
-    return fail(GANET_E_INVALID, "ganet_sga_forward: null pointer");
-  GA_TRY(check_dims5("ganet_sga_forward", N, C, D, H, W));
-  if (D > 65535) return fail(GANET_E_UNSUPPORTED, "ganet_sga_forward: D > 65535");
+  const char *who = "ganet_sga_forward";
+  GA_TRY(check_ptrs(who, x, g0, g1, g2, g3, A_ws, out, mask, kp));
+  GA_TRY(check_dims5(who, N, C, D, H, W));
+  if (D > 65535) return fail(GANET_E_UNSUPPORTED, "%s: D > 65535", who);
   const i64 n = (i64)N * C * D * H * W;
   hipStream_t st = (hipStream_t)stream;
   const float *gs[4] = {g0, g1, g2, g3};
@@ -918,18 +933,19 @@ namespace {
 bool infer_fused_ok(const float *x, const float *g0, const float *g1, const float *g2, const float *g3, const float *out,
                     int N, int C, int D, int W)
 {
-  const bool all_al = aligned16(x) && aligned16(out) && aligned16(g0) && aligned16(g1) && aligned16(g2) && aligned16(g3);
-  return all_al && N * C <= 65535 && rowwave_ok(D, W, 2, row_smem_fwd(D)) &&
-         colblock_ok(D, W, 0, col_smem_fwd(D));
+  // (H does not enter either family's test)
+  const bool all_al = aligned16(x, out, g0, g1, g2, g3);
+  return scan_family_ok(SCAN_ROW_WAVE, {N, C, D, 0, W, 2, false, all_al}) &&
+         scan_family_ok(SCAN_COL_BLOCK, {N, C, D, 0, W, 0, false, all_al});
 }
 }  // namespace
 
 GA_EXPORT int ganet_sga_forward_infer_scratch(const float *x, const float *g0, const float *g1, const float *g2,
                                               const float *g3, const float *out, int N, int C, int D, int H, int W)
 {
-  if (!x || !g0 || !g1 || !g2 || !g3 || !out)
-    return fail(GANET_E_INVALID, "ganet_sga_forward_infer_scratch: null pointer");
-  GA_TRY(check_dims5("ganet_sga_forward_infer_scratch", N, C, D, H, W));
+  const char *who = "ganet_sga_forward_infer_scratch";
+  GA_TRY(check_ptrs(who, x, g0, g1, g2, g3, out));
+  GA_TRY(check_dims5(who, N, C, D, H, W));
   return infer_fused_ok(x, g0, g1, g2, g3, out, N, C, D, W) ? 0 : 4;
 }
 
@@ -938,11 +954,10 @@ GA_EXPORT int ganet_sga_forward_infer(const float *x, const float *g0, const flo
                                       const float *bn_shift, int N, int C, int D, int H, int W,
                                       void *stream)
 {
-  if (!x || !g0 || !g1 || !g2 || !g3 || !out)
-    return fail(GANET_E_INVALID, "ganet_sga_forward_infer: null pointer");
-  if ((bn_scale == nullptr) != (bn_shift == nullptr))
-    return fail(GANET_E_INVALID, "ganet_sga_forward_infer: bn_scale and bn_shift go together");
-  GA_TRY(check_dims5("ganet_sga_forward_infer", N, C, D, H, W));
+  const char *who = "ganet_sga_forward_infer";
+  GA_TRY(check_ptrs(who, x, g0, g1, g2, g3, out));
+  if ((bn_scale == nullptr) != (bn_shift == nullptr)) return fail(GANET_E_INVALID, "%s: bn_scale and bn_shift go together", who);
+  GA_TRY(check_dims5(who, N, C, D, H, W));
   const i64 n = (i64)N * C * D * H * W;
   const i64 slice = (i64)D * H * W;
   hipStream_t st = (hipStream_t)stream;
@@ -956,14 +971,13 @@ GA_EXPORT int ganet_sga_forward_infer(const float *x, const float *g0, const flo
     GA_TRY(row_fwd(x, g2, out, N * C, D, H, W, 2, st, 1));
     return row_fwd(x, g3, out, N * C, D, H, W, 3, st, bn_scale ? 2 : 1, C, bn_scale, bn_shift);
   }
-  if (!A_ws) return fail(GANET_E_INVALID, "ganet_sga_forward_infer: this shape needs the A_ws scratch (see ganet_sga_forward_infer_scratch)");
+  if (!A_ws) return fail(GANET_E_INVALID, "%s: this shape needs the A_ws scratch (see ganet_sga_forward_infer_scratch)", who);
   for (int d = 0; d < 4; d++) GA_TRY(scan_fwd(x, gs[d], A_ws + d * n, N, C, D, H, W, d, st));
-  if (slice % 4 == 0 && aligned16(A_ws) && aligned16(out))
-    GA_LAUNCH((sga_merge_infer<true>), dim3(ew_grid(n / 4)), dim3(256), st, A_ws, A_ws + n, A_ws + 2 * n, A_ws + 3 * n,
-              out, bn_scale, bn_shift, C, slice, n);
-  else
-    GA_LAUNCH((sga_merge_infer<false>), dim3(ew_grid(n)), dim3(256), st, A_ws, A_ws + n, A_ws + 2 * n, A_ws + 3 * n,
-              out, bn_scale, bn_shift, C, slice, n);
+  const bool vec = slice % 4 == 0 && aligned16(A_ws, out);
+  with_flags([&](auto v) {
+    GA_LAUNCH((sga_merge_infer<decltype(v)::value>), dim3(ew_grid(vec ? n / 4 : n)), dim3(256), st, A_ws, A_ws + n, A_ws + 2 * n,
+              A_ws + 3 * n, out, bn_scale, bn_shift, C, slice, n);
+  }, vec);
   return check_launch("sga merge (inference)");
 }
 
@@ -971,10 +985,10 @@ GA_EXPORT int ganet_sga_backward_scan(const float *g, const uint8_t *mask, const
                                       const float *grad_out, float *G, int N, int C, int D, int H,
                                       int W, int dir, void *stream)
 {
-  if (!g || !mask || !kp_dir || !grad_out || !G)
-    return fail(GANET_E_INVALID, "ganet_sga_backward_scan: null pointer");
-  if (dir < 0 || dir > 3) return fail(GANET_E_INVALID, "ganet_sga_backward_scan: dir %d", dir);
-  GA_TRY(check_dims5("ganet_sga_backward_scan", N, C, D, H, W));
+  const char *who = "ganet_sga_backward_scan";
+  GA_TRY(check_ptrs(who, g, mask, kp_dir, grad_out, G));
+  GA_TRY(check_dir(who, dir));
+  GA_TRY(check_dims5(who, N, C, D, H, W));
   return scan_bwdg(g, mask, kp_dir, grad_out, G, N, C, D, H, W, dir, (hipStream_t)stream);
 }
 
@@ -984,10 +998,10 @@ GA_EXPORT int ganet_sga_backward_dir(const float *x, const float *g, const float
                                      int N, int C, int D, int H, int W, int dir, int accumulate,
                                      void *stream)
 {
-  if (!x || !g || !A || !mask || !kp_dir || !grad_out || !G_ws || !grad_x || !gw)
-    return fail(GANET_E_INVALID, "ganet_sga_backward_dir: null pointer");
-  if (dir < 0 || dir > 3) return fail(GANET_E_INVALID, "ganet_sga_backward_dir: dir %d", dir);
-  GA_TRY(check_dims5("ganet_sga_backward_dir", N, C, D, H, W));
+  const char *who = "ganet_sga_backward_dir";
+  GA_TRY(check_ptrs(who, x, g, A, mask, kp_dir, grad_out, G_ws, grad_x, gw));
+  GA_TRY(check_dir(who, dir));
+  GA_TRY(check_dims5(who, N, C, D, H, W));
   hipStream_t st = (hipStream_t)stream;
   GA_TRY(scan_bwdg(g, mask, kp_dir, grad_out, G_ws, N, C, D, H, W, dir, st));
   PointArgs pa = {};
@@ -1017,9 +1031,9 @@ GA_EXPORT int ganet_sga_backward_point(const float *x, const float *g0, const fl
                                         const float *A_ws, const float *G_ws, float *grad_x, float *gw0, float *gw1, float *gw2,
                                         float *gw3, int N, int C, int D, int H, int W, void *stream)
 {
-  if (!x || !g0 || !g1 || !g2 || !g3 || !A_ws || !G_ws || !grad_x || !gw0 || !gw1 || !gw2 || !gw3)
-    return fail(GANET_E_INVALID, "ganet_sga_backward_point: null pointer");
-  GA_TRY(check_dims5("ganet_sga_backward_point", N, C, D, H, W));
+  const char *who = "ganet_sga_backward_point";
+  GA_TRY(check_ptrs(who, x, g0, g1, g2, g3, A_ws, G_ws, grad_x, gw0, gw1, gw2, gw3));
+  GA_TRY(check_dims5(who, N, C, D, H, W));
   // pairs with ganet_sga_backward_scan_ws, which keeps G_down / G_up in the layout ganet_sga_workspace_layout reports
   return backward_point_impl(x, g0, g1, g2, g3, A_ws, G_ws, grad_x, gw0, gw1, gw2, gw3, N, C, D, H, W, (hipStream_t)stream,
                              sga_ws_tiled(N, C, D, H, W));
@@ -1031,18 +1045,16 @@ GA_EXPORT int ganet_sga_backward(const float *x, const float *g0, const float *g
                                  float *grad_x, float *gw0, float *gw1, float *gw2, float *gw3,
                                  int N, int C, int D, int H, int W, void *stream)
 {
-  if (!x || !g0 || !g1 || !g2 || !g3 || !A_ws || !mask || !kp || !grad_out || !G_ws || !grad_x ||
-      !gw0 || !gw1 || !gw2 || !gw3)
-    return fail(GANET_E_INVALID, "ganet_sga_backward: null pointer");
-  GA_TRY(check_dims5("ganet_sga_backward", N, C, D, H, W));
+  const char *who = "ganet_sga_backward";
+  GA_TRY(check_ptrs(who, x, g0, g1, g2, g3, A_ws, mask, kp, grad_out, G_ws, grad_x, gw0, gw1, gw2, gw3));
+  GA_TRY(check_dims5(who, N, C, D, H, W));
   const i64 n = (i64)N * C * D * H * W;
   const i64 npix = (i64)N * C * H * W;
   hipStream_t st = (hipStream_t)stream;
   const float *gs[4] = {g0, g1, g2, g3};
   // The layout of G_down / G_up is private to this call: decided ONCE, from the dimensions, the options and the alignment of what
   // the tiled column kernels touch (a contiguous but 4-byte aligned gradient takes the API layout and the generic scans).
-  const int tiled = sga_ws_tiled(N, C, D, H, W) && aligned16(g0) && aligned16(g1) && aligned16(grad_out) && aligned16(G_ws) &&
-                    (n % 4 == 0) && (((uintptr_t)mask & 3) == 0);
+  const int tiled = sga_ws_tiled(N, C, D, H, W, aligned16(g0, g1, grad_out, G_ws) && (n % 4 == 0), aligned4(mask));
   for (int d = 0; d < 4; d++)
     GA_TRY(scan_bwdg(gs[d], mask, kp + d * npix, grad_out, G_ws + d * n, N, C, D, H, W, d, st, d < 2 && tiled));
   return backward_point_impl(x, g0, g1, g2, g3, A_ws, G_ws, grad_x, gw0, gw1, gw2, gw3, N, C, D, H, W, st, tiled);
@@ -1053,9 +1065,9 @@ GA_EXPORT int ganet_sga_forward_compat(const float *x, const float *g0, const fl
                                        float *out, float *mask_f32, int N, int C, int D, int H,
                                        int W, void *stream)
 {
-  if (!x || !g0 || !g1 || !g2 || !g3 || !temp_out || !out || !mask_f32)
-    return fail(GANET_E_INVALID, "ganet_sga_forward_compat: null pointer");
-  GA_TRY(check_dims5("ganet_sga_forward_compat", N, C, D, H, W));
+  const char *who = "ganet_sga_forward_compat";
+  GA_TRY(check_ptrs(who, x, g0, g1, g2, g3, temp_out, out, mask_f32));
+  GA_TRY(check_dims5(who, N, C, D, H, W));
   const i64 n = (i64)N * C * D * H * W;
   hipStream_t st = (hipStream_t)stream;
   const float *gs[4] = {g0, g1, g2, g3};
@@ -1076,11 +1088,10 @@ GA_EXPORT int ganet_sga_backward_compat(const float *x, const float *g0, const f
                                         float *gw0, float *gw1, float *gw2, float *gw3, int N,
                                         int C, int D, int H, int W, void *stream)
 {
-  if (!x || !g0 || !g1 || !g2 || !g3 || !temp_out || !mask_f32 || !max_idx || !grad_out ||
-      !temp_grad || !grad_x || !gw0 || !gw1 || !gw2 || !gw3)
-    return fail(GANET_E_INVALID, "ganet_sga_backward_compat: null pointer");
-  GA_TRY(check_dims5("ganet_sga_backward_compat", N, C, D, H, W));
-  if (D > 65535) return fail(GANET_E_UNSUPPORTED, "ganet_sga_backward_compat: D > 65535");
+  const char *who = "ganet_sga_backward_compat";
+  GA_TRY(check_ptrs(who, x, g0, g1, g2, g3, temp_out, mask_f32, max_idx, grad_out, temp_grad, grad_x, gw0, gw1, gw2, gw3));
+  GA_TRY(check_dims5(who, N, C, D, H, W));
+  if (D > 65535) return fail(GANET_E_UNSUPPORTED, "%s: D > 65535", who);
   const i64 npix = (i64)N * C * H * W;
   hipStream_t st = (hipStream_t)stream;
   // scratch roles as in the reference: temp_out = A_dir, temp_grad = adjoint volume,
@@ -1106,13 +1117,13 @@ GA_EXPORT int ganet_sga_backward_compat(const float *x, const float *g0, const f
 GA_EXPORT int ganet_lga_forward(const float *x, const float *f, float *y, int B, int D, int H,
                                 int W, int radius, void *stream)
 {
-  if (!x || !f || !y) return fail(GANET_E_INVALID, "ganet_lga_forward: null pointer");
-  if (x == y) return fail(GANET_E_INVALID, "ganet_lga_forward: y must not alias x");
-  GA_TRY(check_lga("ganet_lga_forward", B, D, H, W, radius));
-  hipStream_t st = (hipStream_t)stream;
-  if (radius == 1) return launch_lga_fwd<1>(x, f, y, B, D, H, W, false, st);
-  if (radius == 2) return launch_lga_fwd<2>(x, f, y, B, D, H, W, false, st);
-  return launch_lga_fwd<3>(x, f, y, B, D, H, W, false, st);
+  const char *who = "ganet_lga_forward";
+  GA_TRY(check_ptrs(who, x, f, y));
+  if (x == y) return fail(GANET_E_INVALID, "%s: y must not alias x", who);
+  GA_TRY(check_lga(who, B, D, H, W, radius));
+  int rc;
+  with_int_else<3, 1, 2>(radius, [&](auto R) { rc = launch_lga_fwd<decltype(R)::value>(x, f, y, B, D, H, W, false, (hipStream_t)stream); });
+  return rc;
 }
 
 namespace {
@@ -1141,17 +1152,19 @@ GA_EXPORT int ganet_lga_apply_paired(const float *x, const float *f, float *y, i
 GA_EXPORT int ganet_lga_apply_paired_edges(const float *x, const float *f, float *y, float *edge, int B, int D, int H, int W, int radius,
                                            int transposed, int x_paired, int y_paired, void *stream)
 {
-  if (!edge) return fail(GANET_E_INVALID, "ganet_lga_apply_paired_edges: null edge buffer");
-  return lga_apply_paired_impl("ganet_lga_apply_paired_edges", x, f, y, edge, B, D, H, W, radius, transposed, x_paired, y_paired, stream);
+  const char *who = "ganet_lga_apply_paired_edges";
+  if (!edge) return fail(GANET_E_INVALID, "%s: null edge buffer", who);
+  return lga_apply_paired_impl(who, x, f, y, edge, B, D, H, W, radius, transposed, x_paired, y_paired, stream);
 }
 
 GA_EXPORT int ganet_lga_filter_grad_paired(const float *x, const float *gy, float *gf, int B, int D, int H, int W, int radius,
                                            int accumulate_gf, int x_paired, int gy_paired, void *stream)
 {
-  if (!x || !gy || !gf) return fail(GANET_E_INVALID, "ganet_lga_filter_grad_paired: null pointer");
-  GA_TRY(check_lga("ganet_lga_filter_grad_paired", B, D, H, W, radius));
-  if (x_paired && gy_paired) return fail(GANET_E_INVALID, "ganet_lga_filter_grad_paired: at most one of x_paired / gy_paired");
-  if (radius != 2) return fail(GANET_E_UNSUPPORTED, "ganet_lga_filter_grad_paired: radius 2 only");
+  const char *who = "ganet_lga_filter_grad_paired";
+  GA_TRY(check_ptrs(who, x, gy, gf));
+  GA_TRY(check_lga(who, B, D, H, W, radius));
+  if (x_paired && gy_paired) return fail(GANET_E_INVALID, "%s: at most one of x_paired / gy_paired", who);
+  if (radius != 2) return fail(GANET_E_UNSUPPORTED, "%s: radius 2 only", who);
   if (!x_paired && !gy_paired) return launch_lga_gf<2>(x, gy, gf, B, D, H, W, accumulate_gf != 0, (hipStream_t)stream);
   return launch_lga_gf_paired(x, gy, gf, B, D, H, W, accumulate_gf != 0, x_paired != 0, (hipStream_t)stream);
 }
@@ -1159,42 +1172,44 @@ GA_EXPORT int ganet_lga_filter_grad_paired(const float *x, const float *gy, floa
 GA_EXPORT int ganet_lga_forward_regress(const float *x, const float *f, float *y, float *snorm, float *sdy, int B, int D,
                                         int H, int W, int radius, void *stream)
 {
-  if (!x || !f || !snorm || !sdy) return fail(GANET_E_INVALID, "ganet_lga_forward_regress: null pointer");
-  if (x == y) return fail(GANET_E_INVALID, "ganet_lga_forward_regress: y must not alias x");
-  GA_TRY(check_lga("ganet_lga_forward_regress", B, D, H, W, radius));
-  hipStream_t st = (hipStream_t)stream;
-  if (radius == 1) return launch_lga_fwd_regress<1>(x, f, y, snorm, sdy, B, D, H, W, st);
-  if (radius == 2) return launch_lga_fwd_regress<2>(x, f, y, snorm, sdy, B, D, H, W, st);
-  return launch_lga_fwd_regress<3>(x, f, y, snorm, sdy, B, D, H, W, st);
+  const char *who = "ganet_lga_forward_regress";
+  GA_TRY(check_ptrs(who, x, f, snorm, sdy));
+  if (x == y) return fail(GANET_E_INVALID, "%s: y must not alias x", who);
+  GA_TRY(check_lga(who, B, D, H, W, radius));
+  int rc;
+  with_int_else<3, 1, 2>(radius, [&](auto R) { rc = launch_lga_fwd_regress<decltype(R)::value>(x, f, y, snorm, sdy, B, D, H, W, (hipStream_t)stream); });
+  return rc;
 }
 
 GA_EXPORT int ganet_lga_backward(const float *x, const float *f, const float *gy, float *gx,
                                  float *gf, int B, int D, int H, int W, int radius,
                                  int accumulate_gf, void *stream)
 {
-  if (!x || !f || !gy || !gx || !gf) return fail(GANET_E_INVALID, "ganet_lga_backward: null pointer");
-  if (gx == gy) return fail(GANET_E_INVALID, "ganet_lga_backward: gx must not alias gy");
-  GA_TRY(check_lga("ganet_lga_backward", B, D, H, W, radius));
+  const char *who = "ganet_lga_backward";
+  GA_TRY(check_ptrs(who, x, f, gy, gx, gf));
+  if (gx == gy) return fail(GANET_E_INVALID, "%s: gx must not alias gy", who);
+  GA_TRY(check_lga(who, B, D, H, W, radius));
   hipStream_t st = (hipStream_t)stream;
   const int acc = accumulate_gf ? 1 : 0;
   // filter gradient first: it is the only consumer of x, so gx may alias x afterwards
   // (the reference's chained LGA2/LGA3 backward relies on that, functions/GANet.py:197).
   // (the two kernels of a pass on two streams: measured slower, 0.215 -> 0.238 ms, profiles/r2m_*)
   int rc;
-  if (radius == 1) { rc = launch_lga_gf<1>(x, gy, gf, B, D, H, W, acc, st); if (rc == GANET_OK) rc = launch_lga_fwd<1>(gy, f, gx, B, D, H, W, true, st); }
-  else if (radius == 2) { rc = launch_lga_gf<2>(x, gy, gf, B, D, H, W, acc, st); if (rc == GANET_OK) rc = launch_lga_fwd<2>(gy, f, gx, B, D, H, W, true, st); }
-  else { rc = launch_lga_gf<3>(x, gy, gf, B, D, H, W, acc, st); if (rc == GANET_OK) rc = launch_lga_fwd<3>(gy, f, gx, B, D, H, W, true, st); }
+  with_int_else<3, 1, 2>(radius, [&](auto R) {
+    rc = launch_lga_gf<decltype(R)::value>(x, gy, gf, B, D, H, W, acc, st);
+    if (rc == GANET_OK) rc = launch_lga_fwd<decltype(R)::value>(gy, f, gx, B, D, H, W, true, st);
+  });
   return rc;
 }
 
 GA_EXPORT int ganet_cost_volume_forward(const float *x, const float *y, float *cost, int N, int C,
                                         int Dn, int H, int W, void *stream)
 {
-  if (!x || !y || !cost) return fail(GANET_E_INVALID, "ganet_cost_volume_forward: null pointer");
-  if (N <= 0 || C <= 0 || Dn <= 0 || H <= 0 || W <= 0)
-    return fail(GANET_E_INVALID, "ganet_cost_volume_forward: non-positive size");
+  const char *who = "ganet_cost_volume_forward";
+  GA_TRY(check_ptrs(who, x, y, cost));
+  GA_TRY(check_positive(who, N, C, Dn, H, W));
   const i64 n = (i64)N * 2 * C * Dn * H * W;
-  if (W % 4 == 0 && aligned16(x) && aligned16(cost))
+  if (W % 4 == 0 && aligned16(x, cost))
     GA_LAUNCH(cost_volume_fwd4, dim3(ew_grid(n / 4)), dim3(256), (hipStream_t)stream, x, y, cost, N, C, Dn, H, W);
   else
     GA_LAUNCH(cost_volume_fwd, dim3(ew_grid(n)), dim3(256), (hipStream_t)stream, x, y, cost, N, C, Dn, H, W);
@@ -1204,10 +1219,9 @@ GA_EXPORT int ganet_cost_volume_forward(const float *x, const float *y, float *c
 GA_EXPORT int ganet_cost_volume_backward(const float *grad_cost, float *grad_x, float *grad_y,
                                          int N, int C, int Dn, int H, int W, void *stream)
 {
-  if (!grad_cost || !grad_x || !grad_y)
-    return fail(GANET_E_INVALID, "ganet_cost_volume_backward: null pointer");
-  if (N <= 0 || C <= 0 || Dn <= 0 || H <= 0 || W <= 0)
-    return fail(GANET_E_INVALID, "ganet_cost_volume_backward: non-positive size");
+  const char *who = "ganet_cost_volume_backward";
+  GA_TRY(check_ptrs(who, grad_cost, grad_x, grad_y));
+  GA_TRY(check_positive(who, N, C, Dn, H, W));
   const i64 n = (i64)N * C * H * W;
   GA_LAUNCH(cost_volume_bwd, dim3(ew_grid(n)), dim3(256), (hipStream_t)stream, grad_cost, grad_x, grad_y, N, C, Dn, H, W);
   return check_launch("cost volume backward");
@@ -1216,9 +1230,9 @@ GA_EXPORT int ganet_cost_volume_backward(const float *grad_cost, float *grad_x, 
 GA_EXPORT int ganet_disparity_regression_forward(const float *x, float *out, int N, int Dn, int H,
                                                  int W, void *stream)
 {
-  if (!x || !out) return fail(GANET_E_INVALID, "ganet_disparity_regression_forward: null pointer");
-  if (N <= 0 || Dn <= 0 || H <= 0 || W <= 0)
-    return fail(GANET_E_INVALID, "ganet_disparity_regression_forward: non-positive size");
+  const char *who = "ganet_disparity_regression_forward";
+  GA_TRY(check_ptrs(who, x, out));
+  GA_TRY(check_positive(who, N, Dn, H, W));
   const i64 HW = (i64)H * W;
   GA_LAUNCH(disp_regression_fwd, dim3(ew_grid((i64)N * HW)), dim3(256), (hipStream_t)stream, x, out, N, Dn, HW);
   return check_launch("disparity regression forward");
@@ -1227,12 +1241,11 @@ GA_EXPORT int ganet_disparity_regression_forward(const float *x, float *out, int
 GA_EXPORT int ganet_disparity_regression_backward(const float *grad_out, float *grad_x, int N,
                                                   int Dn, int H, int W, void *stream)
 {
-  if (!grad_out || !grad_x)
-    return fail(GANET_E_INVALID, "ganet_disparity_regression_backward: null pointer");
-  if (N <= 0 || Dn <= 0 || H <= 0 || W <= 0)
-    return fail(GANET_E_INVALID, "ganet_disparity_regression_backward: non-positive size");
+  const char *who = "ganet_disparity_regression_backward";
+  GA_TRY(check_ptrs(who, grad_out, grad_x));
+  GA_TRY(check_positive(who, N, Dn, H, W));
   const i64 HW = (i64)H * W;
-  if (HW % 4 == 0 && aligned16(grad_out) && aligned16(grad_x))
+  if (HW % 4 == 0 && aligned16(grad_out, grad_x))
     GA_LAUNCH(disp_regression_bwd4, dim3(ew_grid((i64)N * (HW / 4))), dim3(256), (hipStream_t)stream, grad_out, grad_x, N, Dn, HW);
   else
     GA_LAUNCH(disp_regression_bwd, dim3(ew_grid((i64)N * Dn * HW)), dim3(256), (hipStream_t)stream, grad_out, grad_x, N, Dn, HW);
@@ -1253,20 +1266,19 @@ int check_norm(const char *who, int N, int G, int C, int K, int H, int W)
 GA_EXPORT int ganet_l1_normalize_forward(const float *x, float *y0, float *y1, float *y2, float *y3,
                                          int N, int G, int C, int K, int H, int W, void *stream)
 {
-  GA_TRY(check_norm("ganet_l1_normalize_forward", N, G, C, K, H, W));
+  const char *who = "ganet_l1_normalize_forward";
+  GA_TRY(check_norm(who, N, G, C, K, H, W));
   float *ys[4] = {y0, y1, y2, y3};
-  if (!x) return fail(GANET_E_INVALID, "ganet_l1_normalize_forward: null pointer");
+  GA_TRY(check_ptrs(who, x));
   NormPtrs p = {};
   for (int g = 0; g < 4; g++) {
-    if (g < G && !ys[g]) return fail(GANET_E_INVALID, "ganet_l1_normalize_forward: null output %d", g);
+    if (g < G && !ys[g]) return fail(GANET_E_INVALID, "%s: null output %d", who, g);
     p.y[g] = ys[g < G ? g : 0];
   }
   const i64 HW = (i64)H * W;
   const dim3 grid(ew_grid((i64)N * G * C * HW)), block(256);
   hipStream_t st = (hipStream_t)stream;
-  if (K == 5) GA_LAUNCH((l1norm_fwd<5>), grid, block, st, x, p, N, G, C, K, HW);
-  else if (K == 75) GA_LAUNCH((l1norm_fwd<75>), grid, block, st, x, p, N, G, C, K, HW);
-  else GA_LAUNCH((l1norm_fwd<0>), grid, block, st, x, p, N, G, C, K, HW);
+  with_int_else<0, 5, 75>(K, [&](auto KC) { GA_LAUNCH((l1norm_fwd<decltype(KC)::value>), grid, block, st, x, p, N, G, C, K, HW); });
   return check_launch("l1 normalise forward");
 }
 
@@ -1274,30 +1286,28 @@ GA_EXPORT int ganet_l1_normalize_backward(const float *x, const float *gy0, cons
                                           const float *gy2, const float *gy3, float *grad_x,
                                           int N, int G, int C, int K, int H, int W, void *stream)
 {
-  GA_TRY(check_norm("ganet_l1_normalize_backward", N, G, C, K, H, W));
+  const char *who = "ganet_l1_normalize_backward";
+  GA_TRY(check_norm(who, N, G, C, K, H, W));
   const float *gs[4] = {gy0, gy1, gy2, gy3};
-  if (!x || !grad_x) return fail(GANET_E_INVALID, "ganet_l1_normalize_backward: null pointer");
+  GA_TRY(check_ptrs(who, x, grad_x));
   NormPtrs p = {};
   for (int g = 0; g < 4; g++) {
-    if (g < G && !gs[g]) return fail(GANET_E_INVALID, "ganet_l1_normalize_backward: null gradient %d", g);
+    if (g < G && !gs[g]) return fail(GANET_E_INVALID, "%s: null gradient %d", who, g);
     p.gy[g] = gs[g < G ? g : 0];
   }
   const i64 HW = (i64)H * W;
   const dim3 grid(ew_grid((i64)N * G * C * HW)), block(256);
   hipStream_t st = (hipStream_t)stream;
-  if (K == 5) GA_LAUNCH((l1norm_bwd<5>), grid, block, st, x, p, grad_x, N, G, C, K, HW);
-  else if (K == 75) GA_LAUNCH((l1norm_bwd<75>), grid, block, st, x, p, grad_x, N, G, C, K, HW);
-  else GA_LAUNCH((l1norm_bwd<0>), grid, block, st, x, p, grad_x, N, G, C, K, HW);
+  with_int_else<0, 5, 75>(K, [&](auto KC) { GA_LAUNCH((l1norm_bwd<decltype(KC)::value>), grid, block, st, x, p, grad_x, N, G, C, K, HW); });
   return check_launch("l1 normalise backward");
 }
 
 GA_EXPORT int ganet_norm_disparity_regression_forward(const float *x, float *out, float *snorm, int N,
                                                       int Dn, int H, int W, void *stream)
 {
-  if (!x || !out || !snorm)
-    return fail(GANET_E_INVALID, "ganet_norm_disparity_regression_forward: null pointer");
-  if (N <= 0 || Dn <= 0 || H <= 0 || W <= 0)
-    return fail(GANET_E_INVALID, "ganet_norm_disparity_regression_forward: non-positive size");
+  const char *who = "ganet_norm_disparity_regression_forward";
+  GA_TRY(check_ptrs(who, x, out, snorm));
+  GA_TRY(check_positive(who, N, Dn, H, W));
   const i64 HW = (i64)H * W;
   GA_LAUNCH(norm_disp_regression_fwd, dim3(ew_grid((i64)N * HW)), dim3(256), (hipStream_t)stream, x, out, snorm, N, Dn, HW);
   return check_launch("normalised disparity regression forward");
@@ -1308,12 +1318,11 @@ GA_EXPORT int ganet_norm_disparity_regression_backward(const float *x, const flo
                                                        float *grad_x, int N, int Dn, int H, int W,
                                                        void *stream)
 {
-  if (!x || !out || !snorm || !grad_out || !grad_x)
-    return fail(GANET_E_INVALID, "ganet_norm_disparity_regression_backward: null pointer");
-  if (N <= 0 || Dn <= 0 || H <= 0 || W <= 0)
-    return fail(GANET_E_INVALID, "ganet_norm_disparity_regression_backward: non-positive size");
+  const char *who = "ganet_norm_disparity_regression_backward";
+  GA_TRY(check_ptrs(who, x, out, snorm, grad_out, grad_x));
+  GA_TRY(check_positive(who, N, Dn, H, W));
   const i64 HW = (i64)H * W;
-  if (HW % 4 == 0 && aligned16(x) && aligned16(out) && aligned16(snorm) && aligned16(grad_out) && aligned16(grad_x))
+  if (HW % 4 == 0 && aligned16(x, out, snorm, grad_out, grad_x))
     GA_LAUNCH(norm_disp_regression_bwd4, dim3(ew_grid((i64)N * (HW / 4))), dim3(256), (hipStream_t)stream, x, out, snorm,
               grad_out, grad_x, N, Dn, HW);
   else
@@ -1325,10 +1334,8 @@ GA_EXPORT int ganet_norm_disparity_regression_backward(const float *x, const flo
 namespace {
 int check_up(const char *who, const void *a, const void *b, int S, int Di, int Hi, int Wi, int Do, int Ho, int Wo)
 {
-  if (!a || !b) return fail(GANET_E_INVALID, "%s: null pointer", who);
-  if (S <= 0 || Di <= 0 || Hi <= 0 || Wi <= 0 || Do <= 0 || Ho <= 0 || Wo <= 0)
-    return fail(GANET_E_INVALID, "%s: non-positive size", who);
-  return GANET_OK;
+  GA_TRY(check_ptrs(who, a, b));
+  return check_positive(who, S, Di, Hi, Wi, Do, Ho, Wo);
 }
 UpAxis up_axis(int in, int out)
 {
@@ -1361,10 +1368,11 @@ GA_EXPORT int ganet_trilinear_upsample_backward(const float *grad_y, float *grad
 
 GA_EXPORT int ganet_softmin_forward(const float *x, float *y, int N, int Dn, int H, int W, void *stream)
 {
-  if (!x || !y) return fail(GANET_E_INVALID, "ganet_softmin_forward: null pointer");
-  if (N <= 0 || Dn <= 0 || H <= 0 || W <= 0) return fail(GANET_E_INVALID, "ganet_softmin_forward: non-positive size");
+  const char *who = "ganet_softmin_forward";
+  GA_TRY(check_ptrs(who, x, y));
+  GA_TRY(check_positive(who, N, Dn, H, W));
   const i64 HW = (i64)H * W;
-  if (HW % 4 == 0 && aligned16(x) && aligned16(y))
+  if (HW % 4 == 0 && aligned16(x, y))
     GA_LAUNCH(softmin_fwd4, dim3(ew_grid((i64)N * HW / 4)), dim3(256), (hipStream_t)stream, x, y, N, Dn, HW);
   else
     GA_LAUNCH(softmin_fwd, dim3(ew_grid((i64)N * HW)), dim3(256), (hipStream_t)stream, x, y, N, Dn, HW);
@@ -1374,10 +1382,11 @@ GA_EXPORT int ganet_softmin_forward(const float *x, float *y, int N, int Dn, int
 GA_EXPORT int ganet_softmin_backward(const float *y, const float *grad_y, float *grad_x, int N, int Dn, int H,
                                      int W, void *stream)
 {
-  if (!y || !grad_y || !grad_x) return fail(GANET_E_INVALID, "ganet_softmin_backward: null pointer");
-  if (N <= 0 || Dn <= 0 || H <= 0 || W <= 0) return fail(GANET_E_INVALID, "ganet_softmin_backward: non-positive size");
+  const char *who = "ganet_softmin_backward";
+  GA_TRY(check_ptrs(who, y, grad_y, grad_x));
+  GA_TRY(check_positive(who, N, Dn, H, W));
   const i64 HW = (i64)H * W;
-  if (HW % 4 == 0 && aligned16(y) && aligned16(grad_y) && aligned16(grad_x))
+  if (HW % 4 == 0 && aligned16(y, grad_y, grad_x))
     GA_LAUNCH(softmin_bwd4, dim3(ew_grid((i64)N * HW / 4)), dim3(256), (hipStream_t)stream, y, grad_y, grad_x, N, Dn, HW);
   else
     GA_LAUNCH(softmin_bwd, dim3(ew_grid((i64)N * HW)), dim3(256), (hipStream_t)stream, y, grad_y, grad_x, N, Dn, HW);
@@ -1387,9 +1396,9 @@ GA_EXPORT int ganet_softmin_backward(const float *y, const float *grad_y, float 
 GA_EXPORT int ganet_softmin_regression_forward(const float *x, float *out, float *mx, float *ssum, int N, int Dn,
                                                int H, int W, void *stream)
 {
-  if (!x || !out || !mx || !ssum) return fail(GANET_E_INVALID, "ganet_softmin_regression_forward: null pointer");
-  if (N <= 0 || Dn <= 0 || H <= 0 || W <= 0)
-    return fail(GANET_E_INVALID, "ganet_softmin_regression_forward: non-positive size");
+  const char *who = "ganet_softmin_regression_forward";
+  GA_TRY(check_ptrs(who, x, out, mx, ssum));
+  GA_TRY(check_positive(who, N, Dn, H, W));
   const i64 HW = (i64)H * W;
   GA_LAUNCH(softmin_regression_fwd, dim3(ew_grid((i64)N * HW)), dim3(256), (hipStream_t)stream, x, out, mx, ssum, N, Dn, HW);
   return check_launch("softmin regression forward");
@@ -1399,10 +1408,9 @@ GA_EXPORT int ganet_softmin_regression_backward(const float *x, const float *out
                                                 const float *ssum, const float *grad_out, float *grad_x,
                                                 int N, int Dn, int H, int W, void *stream)
 {
-  if (!x || !out || !mx || !ssum || !grad_out || !grad_x)
-    return fail(GANET_E_INVALID, "ganet_softmin_regression_backward: null pointer");
-  if (N <= 0 || Dn <= 0 || H <= 0 || W <= 0)
-    return fail(GANET_E_INVALID, "ganet_softmin_regression_backward: non-positive size");
+  const char *who = "ganet_softmin_regression_backward";
+  GA_TRY(check_ptrs(who, x, out, mx, ssum, grad_out, grad_x));
+  GA_TRY(check_positive(who, N, Dn, H, W));
   const i64 HW = (i64)H * W;
   GA_LAUNCH(softmin_regression_bwd, dim3(ew_grid((i64)N * HW)), dim3(256), (hipStream_t)stream, x, out, mx, ssum,
             grad_out, grad_x, N, Dn, HW);
@@ -1413,8 +1421,7 @@ GA_EXPORT int ganet_softmin_regression_backward(const float *x, const float *out
 namespace {
 int check_up_tail(const char *who, int N, int Di, int Hi, int Wi, int Do, int Ho, int Wo)
 {
-  if (N <= 0 || Di <= 0 || Hi <= 0 || Wi <= 0 || Do <= 0 || Ho <= 0 || Wo <= 0)
-    return fail(GANET_E_INVALID, "%s: non-positive size", who);
+  GA_TRY(check_positive(who, N, Di, Hi, Wi, Do, Ho, Wo));
   if (Do >= (1 << 24)) return fail(GANET_E_INVALID, "%s: Do=%d, the disparity index must be exact in float (Do < 2^24)", who, Do);
   return GANET_OK;
 }
@@ -1424,8 +1431,9 @@ int check_up_tail(const char *who, int N, int Di, int Hi, int Wi, int Do, int Ho
 GA_EXPORT int ganet_up_softmin_regression_forward(const float *x, float *out, float *mx, float *ssum, int N, int Di, int Hi,
                                                   int Wi, int Do, int Ho, int Wo, void *stream)
 {
-  if (!x || !out || !mx || !ssum) return fail(GANET_E_INVALID, "ganet_up_softmin_regression_forward: null pointer");
-  GA_TRY(check_up_tail("ganet_up_softmin_regression_forward", N, Di, Hi, Wi, Do, Ho, Wo));
+  const char *who = "ganet_up_softmin_regression_forward";
+  GA_TRY(check_ptrs(who, x, out, mx, ssum));
+  GA_TRY(check_up_tail(who, N, Di, Hi, Wi, Do, Ho, Wo));
   GA_LAUNCH(up_softmin_regression_fwd, dim3(ew_grid((i64)N * Ho * Wo)), dim3(256), (hipStream_t)stream, x, out, mx, ssum,
             (i64)N, up_axis(Di, Do), up_axis(Hi, Ho), up_axis(Wi, Wo));
   return check_launch("up-sampled softmin regression forward");
@@ -1437,9 +1445,9 @@ GA_EXPORT int ganet_up_softmin_regression_backward(const float *x, const float *
                                                    const float *grad_out, float *gcol_ws, float *grad_x, int N, int Di,
                                                    int Hi, int Wi, int Do, int Ho, int Wo, void *stream)
 {
-  if (!x || !out || !mx || !ssum || !grad_out || !gcol_ws || !grad_x)
-    return fail(GANET_E_INVALID, "ganet_up_softmin_regression_backward: null pointer");
-  GA_TRY(check_up_tail("ganet_up_softmin_regression_backward", N, Di, Hi, Wi, Do, Ho, Wo));
+  const char *who = "ganet_up_softmin_regression_backward";
+  GA_TRY(check_ptrs(who, x, out, mx, ssum, grad_out, gcol_ws, grad_x));
+  GA_TRY(check_up_tail(who, N, Di, Hi, Wi, Do, Ho, Wo));
   GA_LAUNCH(up_softmin_regression_bwd_cols, dim3(ew_grid((i64)N * Ho * Wo)), dim3(256), (hipStream_t)stream, x, out, mx, ssum,
             grad_out, gcol_ws, (i64)N, up_axis(Di, Do), up_axis(Hi, Ho), up_axis(Wi, Wo));
   GA_TRY(check_launch("up-sampled softmin regression backward (columns)"));
@@ -1453,8 +1461,7 @@ GA_EXPORT int ganet_up_softmin_regression_backward(const float *x, const float *
 namespace {
 int check_disp_conv(const char *who, int N, int C, int D, int H, int W, DispConvGeom &g, dim3 &grid)
 {
-  if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0)
-    return fail(GANET_E_INVALID, "%s: non-positive size N=%d C=%d D=%d H=%d W=%d", who, N, C, D, H, W);
+  GA_TRY(check_ncdhw(who, N, C, D, H, W));
   if (C > DCV_MAX_C) return fail(GANET_E_UNSUPPORTED, "%s: C=%d, at most %d channels", who, C, DCV_MAX_C);
   g.N = N; g.C = C; g.D = D; g.H = H; g.W = W;
   g.W4 = (W + DCV_PX - 1) / DCV_PX;
@@ -1470,66 +1477,61 @@ i64 disp_conv_rows(const dim3 &grid) { return (i64)grid.x * grid.y * grid.z; }
 
 GA_EXPORT int ganet_disp_conv_workspace(int N, int C, int D, int H, int W)
 {
+  const char *who = "ganet_disp_conv_workspace";
   DispConvGeom g;
   dim3 grid;
-  GA_TRY(check_disp_conv("ganet_disp_conv_workspace", N, C, D, H, W, g, grid));
+  GA_TRY(check_disp_conv(who, N, C, D, H, W, g, grid));
   const i64 n = disp_conv_rows(grid) * 27 * C;
-  if (n > 0x7fffffff) return fail(GANET_E_UNSUPPORTED, "ganet_disp_conv_workspace: %lld elements do not fit the answer", n);
+  if (n > 0x7fffffff) return fail(GANET_E_UNSUPPORTED, "%s: %lld elements do not fit the answer", who, n);
   return (int)n;
 }
 
 GA_EXPORT int ganet_disp_conv_forward(const float *x, const float *weight, float *y, int N, int C, int D, int H, int W,
                                       void *stream)
 {
-  if (!x || !weight || !y) return fail(GANET_E_INVALID, "ganet_disp_conv_forward: null pointer");
+  const char *who = "ganet_disp_conv_forward";
+  GA_TRY(check_ptrs(who, x, weight, y));
   DispConvGeom g;
   dim3 grid;
-  GA_TRY(check_disp_conv("ganet_disp_conv_forward", N, C, D, H, W, g, grid));
-  if (y == x || y == weight) return fail(GANET_E_INVALID, "ganet_disp_conv_forward: y must not alias an input");
+  GA_TRY(check_disp_conv(who, N, C, D, H, W, g, grid));
+  if (y == x || y == weight) return fail(GANET_E_INVALID, "%s: y must not alias an input", who);
   const dim3 block(64 * DCV_WAVES);
-  if (W % 4 == 0 && aligned16(x) && aligned16(y))
-    GA_LAUNCH((disp_conv_fwd<true>), grid, block, (hipStream_t)stream, x, weight, y, g);
-  else
-    GA_LAUNCH((disp_conv_fwd<false>), grid, block, (hipStream_t)stream, x, weight, y, g);
+  with_flags([&](auto v) { GA_LAUNCH((disp_conv_fwd<decltype(v)::value>), grid, block, (hipStream_t)stream, x, weight, y, g); },
+             W % 4 == 0 && aligned16(x, y));
   return check_launch("disp conv forward");
 }
 
 GA_EXPORT int ganet_disp_conv_backward_data(const float *grad_y, const float *weight, float *grad_x, int N, int C, int D,
                                             int H, int W, void *stream)
 {
-  if (!grad_y || !weight || !grad_x) return fail(GANET_E_INVALID, "ganet_disp_conv_backward_data: null pointer");
+  const char *who = "ganet_disp_conv_backward_data";
+  GA_TRY(check_ptrs(who, grad_y, weight, grad_x));
   DispConvGeom g;
   dim3 grid;
-  GA_TRY(check_disp_conv("ganet_disp_conv_backward_data", N, C, D, H, W, g, grid));
-  if (grad_x == grad_y || grad_x == weight)
-    return fail(GANET_E_INVALID, "ganet_disp_conv_backward_data: grad_x must not alias an input");
+  GA_TRY(check_disp_conv(who, N, C, D, H, W, g, grid));
+  if (grad_x == grad_y || grad_x == weight) return fail(GANET_E_INVALID, "%s: grad_x must not alias an input", who);
   const dim3 block(64 * DCV_WAVES);
-  if (W % 4 == 0 && aligned16(grad_y) && aligned16(grad_x))
-    GA_LAUNCH((disp_conv_bwd_data<true>), grid, block, (hipStream_t)stream, grad_y, weight, grad_x, g);
-  else
-    GA_LAUNCH((disp_conv_bwd_data<false>), grid, block, (hipStream_t)stream, grad_y, weight, grad_x, g);
+  with_flags([&](auto v) { GA_LAUNCH((disp_conv_bwd_data<decltype(v)::value>), grid, block, (hipStream_t)stream, grad_y, weight, grad_x, g); },
+             W % 4 == 0 && aligned16(grad_y, grad_x));
   return check_launch("disp conv backward (data)");
 }
 
 GA_EXPORT int ganet_disp_conv_backward_weight(const float *x, const float *grad_y, float *workspace, float *grad_weight,
                                               int N, int C, int D, int H, int W, void *stream)
 {
-  if (!x || !grad_y || !workspace || !grad_weight)
-    return fail(GANET_E_INVALID, "ganet_disp_conv_backward_weight: null pointer");
+  const char *who = "ganet_disp_conv_backward_weight";
+  GA_TRY(check_ptrs(who, x, grad_y, workspace, grad_weight));
   DispConvGeom g;
   dim3 grid;
-  GA_TRY(check_disp_conv("ganet_disp_conv_backward_weight", N, C, D, H, W, g, grid));
+  GA_TRY(check_disp_conv(who, N, C, D, H, W, g, grid));
   if (grad_weight == x || grad_weight == grad_y || workspace == x || workspace == grad_y || workspace == grad_weight)
-    return fail(GANET_E_INVALID, "ganet_disp_conv_backward_weight: workspace and grad_weight must not alias anything");
+    return fail(GANET_E_INVALID, "%s: workspace and grad_weight must not alias anything", who);
   const i64 rows = disp_conv_rows(grid);
-  if (rows * 27 * C > 0x7fffffff)
-    return fail(GANET_E_UNSUPPORTED, "ganet_disp_conv_backward_weight: the workspace is beyond ganet_disp_conv_workspace's answer");
+  if (rows * 27 * C > 0x7fffffff) return fail(GANET_E_UNSUPPORTED, "%s: the workspace is beyond ganet_disp_conv_workspace's answer", who);
   const dim3 block(64 * DCV_WAVES);
   hipStream_t st = (hipStream_t)stream;
-  if (W % 4 == 0 && aligned16(x) && aligned16(grad_y))
-    GA_LAUNCH((disp_conv_bwd_weight_partials<true>), grid, block, st, x, grad_y, workspace, g);
-  else
-    GA_LAUNCH((disp_conv_bwd_weight_partials<false>), grid, block, st, x, grad_y, workspace, g);
+  with_flags([&](auto v) { GA_LAUNCH((disp_conv_bwd_weight_partials<decltype(v)::value>), grid, block, st, x, grad_y, workspace, g); },
+             W % 4 == 0 && aligned16(x, grad_y));
   GA_TRY(check_launch("disp conv backward (weight partials)"));
   const int K = 27 * C;
   GA_LAUNCH(disp_conv_bwd_weight_sum, dim3((unsigned)((K + DCV_SUM_COLS - 1) / DCV_SUM_COLS)),
@@ -1539,12 +1541,6 @@ GA_EXPORT int ganet_disp_conv_backward_weight(const float *x, const float *grad_
 
 // ---- SGABlock's residual epilogue (models/GANet_deep.py:270-277) --------------------
 namespace {
-int check_residual(const char *who, int N, int C, int D, int H, int W)
-{
-  if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0)
-    return fail(GANET_E_INVALID, "%s: non-positive size N=%d C=%d D=%d H=%d W=%d", who, N, C, D, H, W);
-  return GANET_OK;
-}
 // x: enough 256-thread blocks per slice to fill the chip about four times over, y: the slices
 dim3 residual_grid(i64 S, i64 per_slice)
 {
@@ -1559,32 +1555,30 @@ dim3 residual_grid(i64 S, i64 per_slice)
 GA_EXPORT int ganet_residual_relu_forward(const float *t, const float *rem, const float *bn_scale, const float *bn_shift,
                                           float *y, int N, int C, int D, int H, int W, void *stream)
 {
-  GA_TRY(check_residual("ganet_residual_relu_forward", N, C, D, H, W));
-  if (!t || !rem || !y) return fail(GANET_E_INVALID, "ganet_residual_relu_forward: null pointer");
-  if ((bn_scale == nullptr) != (bn_shift == nullptr))
-    return fail(GANET_E_INVALID, "ganet_residual_relu_forward: bn_scale and bn_shift come together");
+  const char *who = "ganet_residual_relu_forward";
+  GA_TRY(check_ncdhw(who, N, C, D, H, W));
+  GA_TRY(check_ptrs(who, t, rem, y));
+  if ((bn_scale == nullptr) != (bn_shift == nullptr)) return fail(GANET_E_INVALID, "%s: bn_scale and bn_shift come together", who);
   const i64 S = (i64)N * C, slice = (i64)D * H * W;
   hipStream_t st = (hipStream_t)stream;
-  if (slice % 4 == 0 && aligned16(t) && aligned16(rem) && aligned16(y))
-    GA_LAUNCH((residual_relu_fwd<true>), residual_grid(S, slice / 4), dim3(256), st, t, rem, bn_scale, bn_shift, y, S, C, slice);
-  else
-    GA_LAUNCH((residual_relu_fwd<false>), residual_grid(S, slice), dim3(256), st, t, rem, bn_scale, bn_shift, y, S, C, slice);
+  const bool vec = slice % 4 == 0 && aligned16(t, rem, y);
+  const dim3 grid = residual_grid(S, vec ? slice / 4 : slice);
+  with_flags([&](auto v) { GA_LAUNCH((residual_relu_fwd<decltype(v)::value>), grid, dim3(256), st, t, rem, bn_scale, bn_shift, y, S, C, slice); }, vec);
   return check_launch("residual + relu forward");
 }
 
 GA_EXPORT int ganet_residual_relu_backward(const float *y, const float *grad_y, const float *bn_scale, float *grad_t,
                                            float *grad_rem, int N, int C, int D, int H, int W, void *stream)
 {
-  GA_TRY(check_residual("ganet_residual_relu_backward", N, C, D, H, W));
-  if (!y || !grad_y || !grad_rem) return fail(GANET_E_INVALID, "ganet_residual_relu_backward: null pointer");
-  if (bn_scale && !grad_t)
-    return fail(GANET_E_INVALID, "ganet_residual_relu_backward: a scaled gradient needs a buffer of its own (grad_t)");
+  const char *who = "ganet_residual_relu_backward";
+  GA_TRY(check_ncdhw(who, N, C, D, H, W));
+  GA_TRY(check_ptrs(who, y, grad_y, grad_rem));
+  if (bn_scale && !grad_t) return fail(GANET_E_INVALID, "%s: a scaled gradient needs a buffer of its own (grad_t)", who);
   const i64 S = (i64)N * C, slice = (i64)D * H * W;
   hipStream_t st = (hipStream_t)stream;
-  if (slice % 4 == 0 && aligned16(y) && aligned16(grad_y) && aligned16(grad_rem) && aligned16(grad_t))
-    GA_LAUNCH((residual_relu_bwd<true>), residual_grid(S, slice / 4), dim3(256), st, y, grad_y, bn_scale, grad_t, grad_rem, S, C, slice);
-  else
-    GA_LAUNCH((residual_relu_bwd<false>), residual_grid(S, slice), dim3(256), st, y, grad_y, bn_scale, grad_t, grad_rem, S, C, slice);
+  const bool vec = slice % 4 == 0 && aligned16(y, grad_y, grad_rem, grad_t);
+  const dim3 grid = residual_grid(S, vec ? slice / 4 : slice);
+  with_flags([&](auto v) { GA_LAUNCH((residual_relu_bwd<decltype(v)::value>), grid, dim3(256), st, y, grad_y, bn_scale, grad_t, grad_rem, S, C, slice); }, vec);
   return check_launch("residual + relu backward");
 }
 
@@ -1609,8 +1603,9 @@ int check_loss(const char *who, const float *const *p, const float *target, cons
 
 GA_EXPORT int ganet_disparity_loss_workspace(int N, int H, int W)
 {
-  if (N <= 0 || H <= 0 || W <= 0) return fail(GANET_E_INVALID, "ganet_disparity_loss_workspace: non-positive size");
-  if ((i64)N * H * W >= (1 << 24)) return fail(GANET_E_UNSUPPORTED, "ganet_disparity_loss_workspace: 2^24 pixels or more");
+  const char *who = "ganet_disparity_loss_workspace";
+  GA_TRY(check_positive(who, N, H, W));
+  if ((i64)N * H * W >= (1 << 24)) return fail(GANET_E_UNSUPPORTED, "%s: 2^24 pixels or more", who);
   return LOSS_MAX_BLOCKS * LOSS_ROW;
 }
 
@@ -1618,10 +1613,11 @@ GA_EXPORT int ganet_disparity_loss_forward(const float *p0, const float *p1, con
                                            const float *params, double *workspace, float *loss, float *stats, int N, int H,
                                            int W, int P, int kind0, int kind1, int kind2, int mask_mode, void *stream)
 {
+  const char *who = "ganet_disparity_loss_forward";
   const float *ps[3] = {p0, p1, p2};
   const int kinds[3] = {kind0, kind1, kind2};
-  GA_TRY(check_loss("ganet_disparity_loss_forward", ps, target, params, N, H, W, P, kinds, mask_mode));
-  if (!workspace || !loss || !stats) return fail(GANET_E_INVALID, "ganet_disparity_loss_forward: null pointer");
+  GA_TRY(check_loss(who, ps, target, params, N, H, W, P, kinds, mask_mode));
+  GA_TRY(check_ptrs(who, workspace, loss, stats));
   LossMaps m = {};
   bool vec = aligned16(target);
   for (int k = 0; k < P; k++) { m.p[k] = ps[k]; m.kind[k] = kinds[k]; vec = vec && aligned16(ps[k]); }
@@ -1630,8 +1626,7 @@ GA_EXPORT int ganet_disparity_loss_forward(const float *p0, const float *p1, con
   const i64 want = ((vec ? total / 4 : total) + LOSS_BLOCK - 1) / LOSS_BLOCK;
   const int rows = (int)(want < LOSS_MAX_BLOCKS ? want : LOSS_MAX_BLOCKS);
   hipStream_t st = (hipStream_t)stream;
-  if (vec) GA_LAUNCH((loss_partials<4>), dim3(rows), dim3(LOSS_BLOCK), st, m, target, params, workspace, total, P, mask_mode);
-  else GA_LAUNCH((loss_partials<1>), dim3(rows), dim3(LOSS_BLOCK), st, m, target, params, workspace, total, P, mask_mode);
+  with_width<4>(vec, [&](auto V) { GA_LAUNCH((loss_partials<decltype(V)::value>), dim3(rows), dim3(LOSS_BLOCK), st, m, target, params, workspace, total, P, mask_mode); });
   GA_TRY(check_launch("disparity loss partial sums"));
   GA_LAUNCH(loss_finish, dim3(1), dim3(64), st, workspace, rows, params, P, loss, stats);
   return check_launch("disparity loss finish");
@@ -1642,23 +1637,24 @@ GA_EXPORT int ganet_disparity_loss_backward(const float *p0, const float *p1, co
                                             float *g1, float *g2, int N, int H, int W, int P, int kind0, int kind1, int kind2,
                                             int mask_mode, void *stream)
 {
+  const char *who = "ganet_disparity_loss_backward";
   const float *ps[3] = {p0, p1, p2};
   float *gs[3] = {g0, g1, g2};
   const int kinds[3] = {kind0, kind1, kind2};
-  GA_TRY(check_loss("ganet_disparity_loss_backward", ps, target, params, N, H, W, P, kinds, mask_mode));
-  if (!stats || !grad_loss) return fail(GANET_E_INVALID, "ganet_disparity_loss_backward: null pointer");
+  GA_TRY(check_loss(who, ps, target, params, N, H, W, P, kinds, mask_mode));
+  GA_TRY(check_ptrs(who, stats, grad_loss));
   LossMaps m = {};
   bool vec = aligned16(target), any = false;
   for (int k = 0; k < P; k++) {
     m.p[k] = ps[k]; m.g[k] = gs[k]; m.kind[k] = kinds[k];
-    if (gs[k]) { any = true; vec = vec && aligned16(ps[k]) && aligned16(gs[k]); }
+    if (gs[k]) { any = true; vec = vec && aligned16(ps[k], gs[k]); }
   }
   if (!any) return GANET_OK;
   const i64 total = (i64)N * H * W;
   vec = vec && total % 4 == 0;
   hipStream_t st = (hipStream_t)stream;
-  if (vec) GA_LAUNCH((loss_bwd<4>), dim3(ew_grid(total / 4)), dim3(256), st, m, target, params, stats, grad_loss, total, P, mask_mode);
-  else GA_LAUNCH((loss_bwd<1>), dim3(ew_grid(total)), dim3(256), st, m, target, params, stats, grad_loss, total, P, mask_mode);
+  const dim3 grid(ew_grid(vec ? total / 4 : total));
+  with_width<4>(vec, [&](auto V) { GA_LAUNCH((loss_bwd<decltype(V)::value>), grid, dim3(256), st, m, target, params, stats, grad_loss, total, P, mask_mode); });
   return check_launch("disparity loss backward");
 }
 
@@ -1670,15 +1666,14 @@ int bn_rows_cap(int C)
   return want < 1 ? 1 : (want < BN_MAX_ROWS ? want : BN_MAX_ROWS);
 }
 
-// rows per channel: Rs blocks along a slice (each lane at least one trip), the rest of the cap over the channel's N slices
-int bn_geom(const char *who, int N, int C, int S, bool vec, bool training, BnGeom *g)
+// rows per channel: Rs blocks along a slice (each lane at least one trip of V elements), the rest of the cap over the channel's N slices
+int bn_geom(const char *who, int N, int C, int S, int V, bool training, BnGeom *g)
 {
   if (N <= 0 || C <= 0 || S <= 0) return fail(GANET_E_INVALID, "%s: non-positive size N=%d C=%d S=%d", who, N, C, S);
-  if (training && (i64)N * S == 1)
-    return fail(GANET_E_INVALID, "%s: one value per channel (N * S = 1): batch statistics need more", who);
+  if (training && (i64)N * S == 1) return fail(GANET_E_INVALID, "%s: one value per channel (N * S = 1): batch statistics need more", who);
   if (C > 65535) return fail(GANET_E_UNSUPPORTED, "%s: C=%d > 65535 (grid.y)", who, C);
   const int cap = bn_rows_cap(C);
-  const i64 want = ((vec ? S / 4 : S) + BN_BLOCK - 1) / BN_BLOCK;
+  const i64 want = (S / V + BN_BLOCK - 1) / BN_BLOCK;
   g->N = N; g->C = C; g->S = S;
   g->Rs = (int)(want < cap ? want : cap);
   g->Rn = cap / g->Rs < N ? cap / g->Rs : N;
@@ -1695,7 +1690,7 @@ float bn_float(int bits)
 GA_EXPORT int ganet_bn_workspace(int N, int C, int S)
 {
   BnGeom g;
-  GA_TRY(bn_geom("ganet_bn_workspace", N, C, S, false, true, &g));
+  GA_TRY(bn_geom("ganet_bn_workspace", N, C, S, 1, true, &g));
   return 2 * C * bn_rows_cap(C);
 }
 
@@ -1705,26 +1700,25 @@ GA_EXPORT int ganet_bn_train_forward(const float *x, const float *rem, const flo
                                      void *stream)
 {
   const char *who = "ganet_bn_train_forward";
-  if (!x || !workspace || !y || !save_mean || !save_invstd) return fail(GANET_E_INVALID, "%s: null pointer", who);
-  if ((running_mean == nullptr) != (running_var == nullptr))
-    return fail(GANET_E_INVALID, "%s: running_mean and running_var come together", who);
+  GA_TRY(check_ptrs(who, x, workspace, y, save_mean, save_invstd));
+  if ((running_mean == nullptr) != (running_var == nullptr)) return fail(GANET_E_INVALID, "%s: running_mean and running_var come together", who);
   if (y == x || y == rem) return fail(GANET_E_INVALID, "%s: y must not alias an input", who);
-  const bool vec = S % 4 == 0 && aligned16(x) && aligned16(y) && aligned16(rem);
+  const bool vec = S % 4 == 0 && aligned16(x, y, rem);
   BnGeom g;
-  GA_TRY(bn_geom(who, N, C, S, vec, true, &g));
+  GA_TRY(bn_geom(who, N, C, S, vec ? 4 : 1, true, &g));
   const float momentum = bn_float(momentum_bits), eps = bn_float(eps_bits);
   const dim3 grid(g.Rs * g.Rn, C);
   hipStream_t st = (hipStream_t)stream;
-  if (vec) GA_LAUNCH((bn_stat_partials<4>), grid, dim3(BN_BLOCK), st, x, workspace, g);
-  else GA_LAUNCH((bn_stat_partials<1>), grid, dim3(BN_BLOCK), st, x, workspace, g);
-  GA_TRY(check_launch("batch norm statistics"));
-  if (vec)
-    GA_LAUNCH((bn_train_apply<4>), grid, dim3(BN_BLOCK), st, x, rem, weight, bias, running_mean, running_var, workspace, y,
+  int rc;
+  with_width<4>(vec, [&](auto v) {
+    constexpr int V = decltype(v)::value;
+    GA_LAUNCH((bn_stat_partials<V>), grid, dim3(BN_BLOCK), st, x, workspace, g);
+    if ((rc = check_launch("batch norm statistics")) != GANET_OK) return;
+    GA_LAUNCH((bn_train_apply<V>), grid, dim3(BN_BLOCK), st, x, rem, weight, bias, running_mean, running_var, workspace, y,
               save_mean, save_invstd, g, momentum, eps, relu);
-  else
-    GA_LAUNCH((bn_train_apply<1>), grid, dim3(BN_BLOCK), st, x, rem, weight, bias, running_mean, running_var, workspace, y,
-              save_mean, save_invstd, g, momentum, eps, relu);
-  return check_launch("batch norm forward");
+    rc = check_launch("batch norm forward");
+  });
+  return rc;
 }
 
 GA_EXPORT int ganet_bn_train_backward(const float *x, const float *rem, const float *grad_y, const float *weight,
@@ -1733,41 +1727,40 @@ GA_EXPORT int ganet_bn_train_backward(const float *x, const float *rem, const fl
                                       int relu, void *stream)
 {
   const char *who = "ganet_bn_train_backward";
-  if (!x || !grad_y || !save_mean || !save_invstd || !workspace) return fail(GANET_E_INVALID, "%s: null pointer", who);
+  GA_TRY(check_ptrs(who, x, grad_y, save_mean, save_invstd, workspace));
   for (const float *o : {(const float *)grad_x, (const float *)grad_rem})
     if (o && (o == x || o == rem || o == grad_y)) return fail(GANET_E_INVALID, "%s: a gradient must not alias an input", who);
   if (grad_x && grad_x == grad_rem) return fail(GANET_E_INVALID, "%s: grad_x and grad_rem are two buffers", who);
-  const bool vec = S % 4 == 0 && aligned16(x) && aligned16(rem) && aligned16(grad_y) && aligned16(grad_x) && aligned16(grad_rem);
+  const bool vec = S % 4 == 0 && aligned16(x, rem, grad_y, grad_x, grad_rem);
   BnGeom g;
-  GA_TRY(bn_geom(who, N, C, S, vec, true, &g));
+  GA_TRY(bn_geom(who, N, C, S, vec ? 4 : 1, true, &g));
   if (!grad_x && !grad_rem && !grad_weight && !grad_bias) return GANET_OK;
   const dim3 grid(g.Rs * g.Rn, C), apply_grid = (grad_x || grad_rem) ? grid : dim3(1, C);
   hipStream_t st = (hipStream_t)stream;
-  if (vec) GA_LAUNCH((bn_bwd_partials<4>), grid, dim3(BN_BLOCK), st, x, rem, grad_y, weight, bias, save_mean, save_invstd, workspace, g, relu);
-  else GA_LAUNCH((bn_bwd_partials<1>), grid, dim3(BN_BLOCK), st, x, rem, grad_y, weight, bias, save_mean, save_invstd, workspace, g, relu);
-  GA_TRY(check_launch("batch norm backward sums"));
-  if (vec)
-    GA_LAUNCH((bn_bwd_apply<4>), apply_grid, dim3(BN_BLOCK), st, x, rem, grad_y, weight, bias, save_mean, save_invstd, workspace,
+  int rc;
+  with_width<4>(vec, [&](auto v) {
+    constexpr int V = decltype(v)::value;
+    GA_LAUNCH((bn_bwd_partials<V>), grid, dim3(BN_BLOCK), st, x, rem, grad_y, weight, bias, save_mean, save_invstd, workspace, g, relu);
+    if ((rc = check_launch("batch norm backward sums")) != GANET_OK) return;
+    GA_LAUNCH((bn_bwd_apply<V>), apply_grid, dim3(BN_BLOCK), st, x, rem, grad_y, weight, bias, save_mean, save_invstd, workspace,
               grad_x, grad_rem, grad_weight, grad_bias, g, relu);
-  else
-    GA_LAUNCH((bn_bwd_apply<1>), apply_grid, dim3(BN_BLOCK), st, x, rem, grad_y, weight, bias, save_mean, save_invstd, workspace,
-              grad_x, grad_rem, grad_weight, grad_bias, g, relu);
-  return check_launch("batch norm backward");
+    rc = check_launch("batch norm backward");
+  });
+  return rc;
 }
 
 GA_EXPORT int ganet_bn_apply_forward(const float *x, const float *rem, const float *scale, const float *shift, float *y, int N,
                                      int C, int S, int relu, void *stream)
 {
   const char *who = "ganet_bn_apply_forward";
-  if (!x || !scale || !shift || !y) return fail(GANET_E_INVALID, "%s: null pointer", who);
+  GA_TRY(check_ptrs(who, x, scale, shift, y));
   if (y == rem) return fail(GANET_E_INVALID, "%s: y may alias x, not rem", who);
-  const bool vec = S % 4 == 0 && aligned16(x) && aligned16(y) && aligned16(rem);
+  const bool vec = S % 4 == 0 && aligned16(x, y, rem);
   BnGeom g;
-  GA_TRY(bn_geom(who, N, C, S, vec, false, &g));
+  GA_TRY(bn_geom(who, N, C, S, vec ? 4 : 1, false, &g));
   const dim3 grid(g.Rs * g.Rn, C);
   hipStream_t st = (hipStream_t)stream;
-  if (vec) GA_LAUNCH((bn_affine_apply<4>), grid, dim3(BN_BLOCK), st, x, rem, scale, shift, y, g, relu);
-  else GA_LAUNCH((bn_affine_apply<1>), grid, dim3(BN_BLOCK), st, x, rem, scale, shift, y, g, relu);
+  with_width<4>(vec, [&](auto V) { GA_LAUNCH((bn_affine_apply<decltype(V)::value>), grid, dim3(BN_BLOCK), st, x, rem, scale, shift, y, g, relu); });
   return check_launch("batch norm apply");
 }
 
@@ -1775,52 +1768,27 @@ GA_EXPORT int ganet_bn_apply_forward(const float *x, const float *rem, const flo
 namespace {
 bool type_code(int t) { return t == GANET_F32 || t == GANET_F16 || t == GANET_BF16; }
 
-template <typename Tx, typename Tr, typename Ty>
-void launch_bn_mixed(bool vec, dim3 grid, hipStream_t st, const void *x, const void *rem, const float *scale, const float *shift,
-                     void *y, const BnGeom &g, int relu)
-{
-  const typename Tx::T *xp = (const typename Tx::T *)x;
-  const typename Tr::T *rp = (const typename Tr::T *)rem;
-  typename Ty::T *yp = (typename Ty::T *)y;
-  if (vec) GA_LAUNCH((bn_affine_apply_mixed<Tx, Tr, Ty, MX_V>), grid, dim3(BN_BLOCK), st, xp, rp, scale, shift, yp, g, relu);
-  else GA_LAUNCH((bn_affine_apply_mixed<Tx, Tr, Ty, 1>), grid, dim3(BN_BLOCK), st, xp, rp, scale, shift, yp, g, relu);
-}
-
-template <typename T16>
-void launch_bn_mixed_of(bool rem16, bool y16, bool vec, dim3 grid, hipStream_t st, const void *x, const void *rem,
-                        const float *scale, const float *shift, void *y, const BnGeom &g, int relu)
-{
-  if (rem16 && y16) launch_bn_mixed<T16, T16, T16>(vec, grid, st, x, rem, scale, shift, y, g, relu);
-  else if (rem16) launch_bn_mixed<T16, T16, st_f32>(vec, grid, st, x, rem, scale, shift, y, g, relu);
-  else if (y16) launch_bn_mixed<T16, st_f32, T16>(vec, grid, st, x, rem, scale, shift, y, g, relu);
-  else launch_bn_mixed<T16, st_f32, st_f32>(vec, grid, st, x, rem, scale, shift, y, g, relu);
-}
+// f(type_c<T>) for the storage type of a type code
+template <class F> void with_storage(int code, F &&f) { with_type<st_f32, st_f16, st_bf16>(code == GANET_F32 ? 0 : code == GANET_F16 ? 1 : 2, f); }
+template <class F> void with_st16(int code, F &&f) { with_type<st_f16, st_bf16>(code == GANET_F16 ? 0 : 1, f); }
 
 template <typename Ts, typename Td>
 void launch_cast(const void *src, void *dst, i64 n, hipStream_t st)
 {
   const typename Ts::T *sp = (const typename Ts::T *)src;
   typename Td::T *dp = (typename Td::T *)dst;
-  if (aligned16(src) && aligned16(dst) && n >= MX_V)
-    GA_LAUNCH((cast_kernel<Ts, Td, MX_V>), dim3(ew_grid(n / MX_V)), dim3(256), st, sp, dp, n);
-  else
-    GA_LAUNCH((cast_kernel<Ts, Td, 1>), dim3(ew_grid(n)), dim3(256), st, sp, dp, n);
-}
-
-template <typename Ts>
-void launch_cast_from(const void *src, void *dst, i64 n, int dst_type, bool same, hipStream_t st)
-{
-  if (dst_type == GANET_F32) launch_cast<Ts, st_f32>(src, dst, n, st);
-  else if (same) launch_cast<st_raw16, st_raw16>(src, dst, n, st);
-  else if (dst_type == GANET_F16) launch_cast<Ts, st_f16>(src, dst, n, st);
-  else launch_cast<Ts, st_bf16>(src, dst, n, st);
+  const bool vec = aligned16(src, dst) && n >= MX_V;
+  with_width<MX_V>(vec, [&](auto v) {
+    constexpr int V = decltype(v)::value;
+    GA_LAUNCH((cast_kernel<Ts, Td, V>), dim3(ew_grid(n / V)), dim3(256), st, sp, dp, n);
+  });
 }
 }  // namespace
 
 GA_EXPORT int ganet_cast(const void *src, void *dst, int n_hi, int n_lo, int src_type, int dst_type, void *stream)
 {
   const char *who = "ganet_cast";
-  if (!src || !dst) return fail(GANET_E_INVALID, "%s: null pointer", who);
+  GA_TRY(check_ptrs(who, src, dst));
   if (!type_code(src_type) || !type_code(dst_type)) return fail(GANET_E_INVALID, "%s: type code %d -> %d", who, src_type, dst_type);
   if (n_hi < 0 || n_lo < 0) return fail(GANET_E_INVALID, "%s: negative count n_hi=%d n_lo=%d", who, n_hi, n_lo);
   const i64 n = ((i64)n_hi << 31) + n_lo;
@@ -1828,9 +1796,11 @@ GA_EXPORT int ganet_cast(const void *src, void *dst, int n_hi, int n_lo, int src
   if (src == dst) return fail(GANET_E_INVALID, "%s: dst must not alias src", who);
   hipStream_t st = (hipStream_t)stream;
   const bool same = src_type == dst_type;
-  if (src_type == GANET_F32) launch_cast_from<st_f32>(src, dst, n, dst_type, same, st);
-  else if (src_type == GANET_F16) launch_cast_from<st_f16>(src, dst, n, dst_type, same, st);
-  else launch_cast_from<st_bf16>(src, dst, n, dst_type, same, st);
+  if (same && dst_type != GANET_F32) launch_cast<st_raw16, st_raw16>(src, dst, n, st);      // 16 bits to the same 16 bits: a copy
+  else
+    with_storage(src_type, [&](auto ts) {
+      with_storage(dst_type, [&](auto td) { launch_cast<typename decltype(ts)::type, typename decltype(td)::type>(src, dst, n, st); });
+    });
   return check_launch("cast");
 }
 
@@ -1838,32 +1808,34 @@ GA_EXPORT int ganet_bn_apply_forward_mixed(const void *x, const void *rem, const
                                            int C, int S, int relu, int x_type, int rem_type, int y_type, void *stream)
 {
   const char *who = "ganet_bn_apply_forward_mixed";
-  if (!x || !scale || !shift || !y) return fail(GANET_E_INVALID, "%s: null pointer", who);
+  GA_TRY(check_ptrs(who, x, scale, shift, y));
   if (!type_code(x_type) || !type_code(rem_type) || !type_code(y_type))
     return fail(GANET_E_INVALID, "%s: type codes x=%d rem=%d y=%d", who, x_type, rem_type, y_type);
   if (y == rem) return fail(GANET_E_INVALID, "%s: y may alias x, not rem", who);
-  if (y == x && (y_type == GANET_F32) != (x_type == GANET_F32))
-    return fail(GANET_E_INVALID, "%s: y may alias x only where both have one width", who);
+  if (y == x && (y_type == GANET_F32) != (x_type == GANET_F32)) return fail(GANET_E_INVALID, "%s: y may alias x only where both have one width", who);
   const bool rem16 = rem != nullptr && rem_type != GANET_F32, y16 = y_type != GANET_F32, x32 = x_type == GANET_F32;
-  if (x32 && !y16)
-    return fail(GANET_E_UNSUPPORTED, "%s: x and y are fp32: that is ganet_bn_apply_forward's case", who);
-  if (x32 && rem16)
-    return fail(GANET_E_UNSUPPORTED, "%s: no kernel for an fp32 x with a 16-bit rem", who);
+  if (x32 && !y16) return fail(GANET_E_UNSUPPORTED, "%s: x and y are fp32: that is ganet_bn_apply_forward's case", who);
+  if (x32 && rem16) return fail(GANET_E_UNSUPPORTED, "%s: no kernel for an fp32 x with a 16-bit rem", who);
   if (!x32 && ((rem16 && rem_type != x_type) || (y16 && y_type != x_type)))
     return fail(GANET_E_UNSUPPORTED, "%s: no kernel for x=%d rem=%d y=%d: 16-bit rem and y have x's format", who, x_type, rem_type, y_type);
-  const bool vec = S % MX_V == 0 && aligned16(x) && aligned16(y) && aligned16(rem);
+  const bool vec = S % MX_V == 0 && aligned16(x, y, rem);
   BnGeom g;
-  GA_TRY(bn_geom(who, N, C, S, false, false, &g));
-  const int cap = bn_rows_cap(C);
-  const i64 want = ((vec ? S / MX_V : S) + BN_BLOCK - 1) / BN_BLOCK;
-  g.Rs = (int)(want < cap ? want : cap);
-  g.Rn = cap / g.Rs < N ? cap / g.Rs : N;
+  GA_TRY(bn_geom(who, N, C, S, vec ? MX_V : 1, false, &g));
   const dim3 grid(g.Rs * g.Rn, C);
   hipStream_t st = (hipStream_t)stream;
-  if (x32 && y_type == GANET_F16) launch_bn_mixed<st_f32, st_f32, st_f16>(vec, grid, st, x, rem, scale, shift, y, g, relu);
-  else if (x32) launch_bn_mixed<st_f32, st_f32, st_bf16>(vec, grid, st, x, rem, scale, shift, y, g, relu);
-  else if (x_type == GANET_F16) launch_bn_mixed_of<st_f16>(rem16, y16, vec, grid, st, x, rem, scale, shift, y, g, relu);
-  else launch_bn_mixed_of<st_bf16>(rem16, y16, vec, grid, st, x, rem, scale, shift, y, g, relu);
+  // the 16-bit format of the call (x's, or y's under an fp32 x); every operand is that or fp32
+  with_st16(x32 ? y_type : x_type, [&](auto t16) {
+    with_flags([&](auto fx, auto r16, auto o16, auto v) {
+      using T16 = typename decltype(t16)::type;
+      using Tx = std::conditional_t<decltype(fx)::value, st_f32, T16>;
+      using Tr = std::conditional_t<decltype(r16)::value, T16, st_f32>;
+      using Ty = std::conditional_t<decltype(o16)::value, T16, st_f32>;
+      // (an fp32 x has an fp32 rem and a 16-bit y: checked above)
+      if constexpr (!decltype(fx)::value || (!decltype(r16)::value && decltype(o16)::value))
+        GA_LAUNCH((bn_affine_apply_mixed<Tx, Tr, Ty, decltype(v)::value ? MX_V : 1>), grid, dim3(BN_BLOCK), st, (const typename Tx::T *)x,
+                  (const typename Tr::T *)rem, scale, shift, (typename Ty::T *)y, g, relu);
+    }, x32, rem16, y16, vec);
+  });
   return check_launch("batch norm apply (mixed)");
 }
 
@@ -1871,13 +1843,13 @@ GA_EXPORT int ganet_cost_volume_forward_16(const void *x, const void *y, void *c
                                            void *stream)
 {
   const char *who = "ganet_cost_volume_forward_16";
-  if (!x || !y || !cost) return fail(GANET_E_INVALID, "%s: null pointer", who);
-  if (N <= 0 || C <= 0 || Dn <= 0 || H <= 0 || W <= 0) return fail(GANET_E_INVALID, "%s: non-positive size", who);
+  GA_TRY(check_ptrs(who, x, y, cost));
+  GA_TRY(check_positive(who, N, C, Dn, H, W));
   if (cost == x || cost == y) return fail(GANET_E_INVALID, "%s: cost must not alias an input", who);
   const i64 n = (i64)N * 2 * C * Dn * H * W;
   const uint16_t *xp = (const uint16_t *)x, *yp = (const uint16_t *)y;
   uint16_t *cp = (uint16_t *)cost;
-  if (W % MX_V == 0 && aligned16(x) && aligned16(cost))
+  if (W % MX_V == 0 && aligned16(x, cost))
     GA_LAUNCH(cost_volume_fwd16, dim3(ew_grid(n / MX_V)), dim3(256), (hipStream_t)stream, xp, yp, cp, N, C, Dn, H, W);
   else
     GA_LAUNCH(cost_volume_fwd16s, dim3(ew_grid(n)), dim3(256), (hipStream_t)stream, xp, yp, cp, N, C, Dn, H, W);
@@ -1890,7 +1862,7 @@ GA_EXPORT int ganet_l1_normalize_forward_mixed(const void *x, float *y0, float *
   const char *who = "ganet_l1_normalize_forward_mixed";
   GA_TRY(check_norm(who, N, G, C, K, H, W));
   float *ys[4] = {y0, y1, y2, y3};
-  if (!x) return fail(GANET_E_INVALID, "%s: null pointer", who);
+  GA_TRY(check_ptrs(who, x));
   if (!type_code(x_type)) return fail(GANET_E_INVALID, "%s: type code %d", who, x_type);
   if (x_type == GANET_F32) return fail(GANET_E_UNSUPPORTED, "%s: x is fp32: that is ganet_l1_normalize_forward's case", who);
   NormPtrs p = {};
@@ -1902,15 +1874,11 @@ GA_EXPORT int ganet_l1_normalize_forward_mixed(const void *x, float *y0, float *
   const dim3 grid(ew_grid((i64)N * G * C * HW)), block(256);
   hipStream_t st = (hipStream_t)stream;
   const uint16_t *xp = (const uint16_t *)x;
-  if (x_type == GANET_F16) {
-    if (K == 5) GA_LAUNCH((l1norm_fwd_mixed<5, st_f16>), grid, block, st, xp, p, N, G, C, K, HW);
-    else if (K == 75) GA_LAUNCH((l1norm_fwd_mixed<75, st_f16>), grid, block, st, xp, p, N, G, C, K, HW);
-    else GA_LAUNCH((l1norm_fwd_mixed<0, st_f16>), grid, block, st, xp, p, N, G, C, K, HW);
-  } else {
-    if (K == 5) GA_LAUNCH((l1norm_fwd_mixed<5, st_bf16>), grid, block, st, xp, p, N, G, C, K, HW);
-    else if (K == 75) GA_LAUNCH((l1norm_fwd_mixed<75, st_bf16>), grid, block, st, xp, p, N, G, C, K, HW);
-    else GA_LAUNCH((l1norm_fwd_mixed<0, st_bf16>), grid, block, st, xp, p, N, G, C, K, HW);
-  }
+  with_st16(x_type, [&](auto t16) {
+    with_int_else<0, 5, 75>(K, [&](auto KC) {
+      GA_LAUNCH((l1norm_fwd_mixed<decltype(KC)::value, typename decltype(t16)::type>), grid, block, st, xp, p, N, G, C, K, HW);
+    });
+  });
   return check_launch("l1 normalise forward (mixed)");
 }
 
@@ -1924,16 +1892,14 @@ int io_rows(i64 pixels)
 
 int io_blocks(i64 units)
 {
-  const i64 want = (units + IO_BLOCK - 1) / IO_BLOCK;
-  return (int)(want < 1 ? 1 : (want < IO_MAX_BLOCKS ? want : IO_MAX_BLOCKS));
+  return clamp_grid(units, IO_BLOCK, IO_MAX_BLOCKS);
 }
 
 int io_check_image(const char *who, int H, int W, int CP)
 {
   if (H <= 0 || W <= 0) return fail(GANET_E_INVALID, "%s: non-positive size H=%d W=%d", who, H, W);
   if (CP != 3 && CP != 4) return fail(GANET_E_INVALID, "%s: CP=%d bytes per pixel, 3 or 4", who, CP);
-  if ((i64)H * W > (1 << 24))
-    return fail(GANET_E_INVALID, "%s: %lld pixels; the integer sums are exact up to 2^24", who, (long long)H * W);
+  if ((i64)H * W > (1 << 24)) return fail(GANET_E_INVALID, "%s: %lld pixels; the integer sums are exact up to 2^24", who, (long long)H * W);
   return GANET_OK;
 }
 
@@ -1957,7 +1923,7 @@ GA_EXPORT int ganet_stereo_input_stats(const uint8_t *left, const uint8_t *right
                                        void *stream)
 {
   const char *who = "ganet_stereo_input_stats";
-  if (!left || !right || !workspace) return fail(GANET_E_INVALID, "%s: null pointer", who);
+  GA_TRY(check_ptrs(who, left, right, workspace));
   GA_TRY(io_check_image(who, H, W, CP));
   IoImage g = {left, right, H, W, CP, io_rows((i64)H * W), (aligned16(left) ? 1 : 0) | (aligned16(right) ? 2 : 0)};
   GA_LAUNCH(io_stats, dim3(g.R, 2), dim3(IO_BLOCK), (hipStream_t)stream, g, (u64 *)workspace);
@@ -1969,21 +1935,20 @@ GA_EXPORT int ganet_stereo_input_apply(const uint8_t *left, const uint8_t *right
                                        int form, void *stream)
 {
   const char *who = "ganet_stereo_input_apply";
-  if (!left || !right || !workspace || !left_out || !right_out) return fail(GANET_E_INVALID, "%s: null pointer", who);
+  GA_TRY(check_ptrs(who, left, right, workspace, left_out, right_out));
   GA_TRY(io_check_image(who, H, W, CP));
   GA_TRY(io_check_window(who, Hc, Wc, oy, ox_left));
   GA_TRY(io_check_window(who, Hc, Wc, oy, ox_right));
   if (form != 0 && form != 1) return fail(GANET_E_INVALID, "%s: form=%d (0: table, 1: direct)", who, form);
   IoImage g = {left, right, H, W, CP, io_rows((i64)H * W), 0};
   IoWindow w = {left_out, right_out, Hc, Wc, oy, ox_left, ox_right};
-  const bool vec = Wc % 4 == 0 && aligned16(left_out) && aligned16(right_out);
+  const bool vec = Wc % 4 == 0 && aligned16(left_out, right_out);
   const dim3 grid(io_blocks((i64)Hc * (vec ? Wc / 4 : Wc)), 2);
   hipStream_t st = (hipStream_t)stream;
   const u64 *ws = (const u64 *)workspace;
-  if (vec && form == 0) GA_LAUNCH((io_apply<4, true>), grid, dim3(IO_BLOCK), st, g, w, ws);
-  else if (vec) GA_LAUNCH((io_apply<4, false>), grid, dim3(IO_BLOCK), st, g, w, ws);
-  else if (form == 0) GA_LAUNCH((io_apply<1, true>), grid, dim3(IO_BLOCK), st, g, w, ws);
-  else GA_LAUNCH((io_apply<1, false>), grid, dim3(IO_BLOCK), st, g, w, ws);
+  with_flags([&](auto v, auto table) {
+    GA_LAUNCH((io_apply<decltype(v)::value ? 4 : 1, decltype(table)::value>), grid, dim3(IO_BLOCK), st, g, w, ws);
+  }, vec, form == 0);
   return check_launch("stereo input apply");
 }
 
@@ -1991,7 +1956,7 @@ GA_EXPORT int ganet_window_f32(const float *src, float *dst, int H, int W, int H
                                int fill_bits, void *stream)
 {
   const char *who = "ganet_window_f32";
-  if (!src || !dst) return fail(GANET_E_INVALID, "%s: null pointer", who);
+  GA_TRY(check_ptrs(who, src, dst));
   if (src == dst) return fail(GANET_E_INVALID, "%s: dst must not alias src", who);
   if (H <= 0 || W <= 0 || (i64)H * W > (1 << 28)) return fail(GANET_E_INVALID, "%s: bad size H=%d W=%d", who, H, W);
   GA_TRY(io_check_window(who, Hc, Wc, oy, ox));
@@ -1999,8 +1964,7 @@ GA_EXPORT int ganet_window_f32(const float *src, float *dst, int H, int W, int H
   const bool vec = Wc % 4 == 0 && aligned16(dst);
   const dim3 grid(io_blocks((i64)Hc * (vec ? Wc / 4 : Wc)));
   hipStream_t st = (hipStream_t)stream;
-  if (vec) GA_LAUNCH((io_window_f32<4>), grid, dim3(IO_BLOCK), st, src, dst, H, W, Hc, Wc, oy, ox, sub, fill);
-  else GA_LAUNCH((io_window_f32<1>), grid, dim3(IO_BLOCK), st, src, dst, H, W, Hc, Wc, oy, ox, sub, fill);
+  with_width<4>(vec, [&](auto V) { GA_LAUNCH((io_window_f32<decltype(V)::value>), grid, dim3(IO_BLOCK), st, src, dst, H, W, Hc, Wc, oy, ox, sub, fill); });
   return check_launch("float window");
 }
 
@@ -2008,7 +1972,7 @@ GA_EXPORT int ganet_disparity_to_u16(const float *disp, uint16_t *out, int Hd, i
                                      int scale_bits, void *stream)
 {
   const char *who = "ganet_disparity_to_u16";
-  if (!disp || !out) return fail(GANET_E_INVALID, "%s: null pointer", who);
+  GA_TRY(check_ptrs(who, disp, out));
   if (Hd <= 0 || Wd <= 0 || h <= 0 || w <= 0 || (i64)Hd * Wd > (1 << 28))
     return fail(GANET_E_INVALID, "%s: bad size Hd=%d Wd=%d h=%d w=%d", who, Hd, Wd, h, w);
   if (oy < 0 || ox < 0 || (i64)oy + h > Hd || (i64)ox + w > Wd)
@@ -2018,54 +1982,60 @@ GA_EXPORT int ganet_disparity_to_u16(const float *disp, uint16_t *out, int Hd, i
   const i64 n = (i64)h * w;
   const dim3 grid(io_blocks(vec ? n / 8 : n));
   hipStream_t st = (hipStream_t)stream;
-  if (vec) GA_LAUNCH((io_disp_u16<8>), grid, dim3(IO_BLOCK), st, disp, out, Wd, h, w, oy, ox, scale);
-  else GA_LAUNCH((io_disp_u16<1>), grid, dim3(IO_BLOCK), st, disp, out, Wd, h, w, oy, ox, scale);
+  with_width<8>(vec, [&](auto V) { GA_LAUNCH((io_disp_u16<decltype(V)::value>), grid, dim3(IO_BLOCK), st, disp, out, Wd, h, w, oy, ox, scale); });
   return check_launch("disparity to 16 bit");
 }
 
-GA_EXPORT int ganet_selftest_dpp_wave(int *scratch_dev, int *host_out, void *stream)
+namespace {
+// copy the probe's `npat` x 64 results back and hold them to expect(lane, out[npat]); `tag`: "" | " (wave)"
+template <class Expect>
+int dpp_selftest_report(const char *tag, int npat, const int *scratch_dev, int *host_out, hipStream_t st, Expect expect)
 {
-  if (!scratch_dev || !host_out) return fail(GANET_E_INVALID, "ganet_selftest_dpp_wave: null pointer");
-  hipStream_t st = (hipStream_t)stream;
-  GA_LAUNCH(dpp_probe_wave, dim3(1), dim3(64), st, scratch_dev);
-  GA_TRY(check_launch("dpp probe (wave)"));
 #if defined(GA_HIPSIM)
-  memcpy(host_out, scratch_dev, sizeof(int) * 4 * 64);
+  memcpy(host_out, scratch_dev, sizeof(int) * npat * 64);
 #else
-  GA_HIP(hipMemcpyAsync(host_out, scratch_dev, sizeof(int) * 4 * 64, hipMemcpyDeviceToHost, st));
+  GA_HIP(hipMemcpyAsync(host_out, scratch_dev, sizeof(int) * npat * 64, hipMemcpyDeviceToHost, st));
   GA_HIP(hipStreamSynchronize(st));
 #endif
   int bad = 0, first_pat = -1, first_lane = -1;
   for (int lane = 0; lane < 64; lane++) {
-    const int expect[4] = {lane < 63 ? lane + 1 : -1, lane > 0 ? lane - 1 : -1, 63, 2016};
-    for (int p = 0; p < 4; p++)
-      if (host_out[p * 64 + lane] != expect[p]) {
+    int want[8];
+    expect(lane, want);
+    for (int p = 0; p < npat; p++)
+      if (host_out[p * 64 + lane] != want[p]) {
         if (!bad) { first_pat = p; first_lane = lane; }
         bad++;
       }
   }
   if (bad)
-    return fail(GANET_E_RUNTIME, "DPP self-test (wave): %d mismatches, first at pattern %d lane %d (got %d)",
+    return fail(GANET_E_RUNTIME, "DPP self-test%s: %d mismatches, first at pattern %d lane %d (got %d)", tag,
                 bad, first_pat, first_lane, host_out[first_pat * 64 + first_lane]);
   return GANET_OK;
+}
+}  // namespace
+
+GA_EXPORT int ganet_selftest_dpp_wave(int *scratch_dev, int *host_out, void *stream)
+{
+  GA_TRY(check_ptrs("ganet_selftest_dpp_wave", scratch_dev, host_out));
+  hipStream_t st = (hipStream_t)stream;
+  GA_LAUNCH(dpp_probe_wave, dim3(1), dim3(64), st, scratch_dev);
+  GA_TRY(check_launch("dpp probe (wave)"));
+  return dpp_selftest_report(" (wave)", 4, scratch_dev, host_out, st, [](int lane, int *expect) {
+    expect[0] = lane < 63 ? lane + 1 : -1;
+    expect[1] = lane > 0 ? lane - 1 : -1;
+    expect[2] = 63;
+    expect[3] = 2016;
+  });
 }
 
 GA_EXPORT int ganet_selftest_dpp(int *scratch_dev, int *host_out, void *stream)
 {
-  if (!scratch_dev || !host_out) return fail(GANET_E_INVALID, "ganet_selftest_dpp: null pointer");
+  GA_TRY(check_ptrs("ganet_selftest_dpp", scratch_dev, host_out));
   hipStream_t st = (hipStream_t)stream;
   GA_LAUNCH(dpp_probe, dim3(1), dim3(64), st, scratch_dev);
   GA_TRY(check_launch("dpp probe"));
-#if defined(GA_HIPSIM)
-  memcpy(host_out, scratch_dev, sizeof(int) * 8 * 64);
-#else
-  GA_HIP(hipMemcpyAsync(host_out, scratch_dev, sizeof(int) * 8 * 64, hipMemcpyDeviceToHost, st));
-  GA_HIP(hipStreamSynchronize(st));
-#endif
-  int bad = 0, first_pat = -1, first_lane = -1;
-  for (int lane = 0; lane < 64; lane++) {
+  return dpp_selftest_report("", 8, scratch_dev, host_out, st, [](int lane, int *expect) {
     const int r = lane & 15, row = lane & ~15;
-    int expect[8];
     expect[0] = lane ^ 1;
     expect[1] = lane ^ 2;
     expect[2] = r < 15 ? lane + 1 : -1;
@@ -2078,14 +2048,5 @@ GA_EXPORT int ganet_selftest_dpp(int *scratch_dev, int *host_out, void *stream)
       if ((l * 37) % 64 > (bk * 37) % 64) bk = l;
     expect[6] = bk;
     expect[7] = 16 * row + 120;
-    for (int p = 0; p < 8; p++)
-      if (host_out[p * 64 + lane] != expect[p]) {
-        if (!bad) { first_pat = p; first_lane = lane; }
-        bad++;
-      }
-  }
-  if (bad)
-    return fail(GANET_E_RUNTIME, "DPP self-test: %d mismatches, first at pattern %d lane %d (got %d)",
-                bad, first_pat, first_lane, host_out[first_pat * 64 + first_lane]);
-  return GANET_OK;
+  });
 }

@@ -61,8 +61,10 @@ def test_case_table_reaches_what_it_claims():
     by = dc.BY_ID
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     capi = open(os.path.join(root, "ganet_amd", "csrc", "ganet_capi.hip")).read()
-    grid = capi[capi.index("int ew_grid(i64 n)"):][:200]
-    assert "(n + 255) / 256" in grid and "if (g > 256 * 16) g = 256 * 16;" in grid and dc.MAX_LANES == 256 * 16 * 256
+    # ew_grid: 256 lanes per block, at most 256 * 16 blocks, through the launchers' one clamp
+    assert "int ew_grid(i64 n) { return clamp_grid(n, 256, 256 * 16); }" in capi and dc.MAX_LANES == 256 * 16 * 256
+    clamp = capi[capi.index("int clamp_grid(i64 count, int per_block, i64 cap)"):][:200]
+    assert "(count + per_block - 1) / per_block;" in clamp and "return (int)(g < 1 ? 1 : (g < cap ? g : cap));" in clamp
     hdr = open(os.path.join(root, "ganet_amd", "csrc", "disp_tail_kernels.h")).read()
     assert f"od0 += {ref.CHUNK})" in hdr
     misc = open(os.path.join(root, "ganet_amd", "csrc", "misc_kernels.h")).read()

@@ -116,6 +116,11 @@ def test_cast_copies_and_across_formats(sim, dev):
         mc.check_cast(sim, dev, every[:4099], fmt, fmt, src_off=1, dst_off=3)
     mc.check_cast(sim, dev, every, mc.F16, mc.BF16)
     mc.check_cast(sim, dev, every, mc.BF16, mc.F16)
+    # the one-element-per-lane forms of the same three: a base that is not 16-byte aligned, and fewer elements than a vector
+    mc.check_cast(sim, dev, table[:1027], mc.F32, mc.F32, src_off=1, dst_off=3)
+    mc.check_cast(sim, dev, table[:7], mc.F32, mc.F32)
+    mc.check_cast(sim, dev, every[:4099], mc.F16, mc.BF16, src_off=1, dst_off=3)
+    mc.check_cast(sim, dev, every[:4099], mc.BF16, mc.F16, src_off=1, dst_off=3)
 
 
 @pytest.mark.parametrize("fmt", FMTS, ids=fmt_id)

@@ -118,6 +118,51 @@ def test_vertical_kernel_families(sim, port_oracle, shape, colblock):
         sim.set_option("GANET_SGA_COLBLOCK", 1)
 
 
+_FALLBACKS = {"GANET_SGA_ROWWAVE": 0, "GANET_SGA_COLBLOCK": 0, "GANET_SGA_WIDE_SCAN": 0, "GANET_SGA_WIDE_COL": 0}
+_DEFAULTS = {"GANET_SGA_ROWWAVE": 1, "GANET_SGA_COLBLOCK": 1, "GANET_SGA_WIDE_SCAN": 1, "GANET_SGA_WIDE_COL": 1}
+_LAUNCHER_ARMS = [
+    # row / column kernels, default options: disparities per lane (5 | 9), D a multiple of it or not
+    ((1, 1, 80, 2, 4), {}, False),        # 5 per lane, D % 5 == 0: the lean recurrence of the 16-lane row kernels, both ways
+    ((1, 1, 82, 2, 4), {}, False),        # 9 per lane, D % 9 != 0: row and column forward
+    # W % 16 == 0 and D no multiple of the lane count: the column adjoint reads its mask rows as 16-byte pieces (3 | 5 | 9 per lane)
+    ((1, 1, 34, 2, 16), {}, False),
+    ((1, 1, 71, 2, 16), {}, False),
+    ((1, 1, 82, 2, 16), {}, False),
+    # 13 per lane in the row kernels (few rows would take the wave-wide segments), D = 13 * 15 and not a multiple; the vertical
+    # scans of these depths are segments of (16, 13)
+    ((1, 1, 195, 2, 4), {"GANET_SGA_WIDE_SCAN": 0}, False),
+    ((1, 1, 200, 2, 4), {"GANET_SGA_WIDE_SCAN": 0}, False),
+    # the segment kernels' (lanes, disparities per lane) pairs (16, 9), (16, 13), (16, 17), (64, 9): D just above the pair below;
+    # the same depths through the reference buffer contract (float mask), and (16, 2) and (64, 17) there
+    ((1, 1, 81, 2, 4), _FALLBACKS, True),
+    ((1, 1, 145, 2, 4), _FALLBACKS, True),
+    ((1, 1, 209, 2, 4), _FALLBACKS, True),
+    ((1, 1, 321, 2, 4), _FALLBACKS, True),
+    ((1, 1, 17, 2, 4), _FALLBACKS, True),
+    ((1, 1, 577, 2, 4), _FALLBACKS, True),
+]
+
+
+@pytest.mark.parametrize("shape,options,compat", _LAUNCHER_ARMS, ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else None)
+def test_launcher_arms_no_other_case_reaches(sim, port_oracle, shape, options, compat):
+    """Arms of the launchers' kernel selection that the shapes above leave out, each at the smallest shape that satisfies the
+    arm's own predicate (a few rows, one column block): forward bit-exact, gradients within the tolerance of the other cases.
+    That tolerance, 2e-5, is used above for depths up to 130; a weight gradient is a float32 sum over D products, whose rounding
+    error grows like sqrt(D), so deeper cases get 2e-5 * sqrt(D / 130) (4.2e-5 at D = 577; the checker's own bar is 1e-4)."""
+    for name, value in options.items():
+        sim.set_option(name, value)
+    try:
+        x, gs, go = pc.sga_inputs(shape, seed=sum(shape))
+        want = _oracle_want(port_oracle, x, gs, go)
+        err = pc.check_sga_forward_backward(sim, DEV, x, gs, go, want)
+        assert max(err.values()) < 2e-5 * max(1.0, shape[2] / 130) ** 0.5, err
+        if compat:
+            pc.check_sga_compat(sim, DEV, x, gs, go, want)
+    finally:
+        for name, value in _DEFAULTS.items():
+            sim.set_option(name, value)
+
+
 def test_dpp_selftest(sim):
     scratch = np.zeros(8 * 64, np.int32)
     host = np.zeros(8 * 64, np.int32)
