@@ -85,13 +85,14 @@ def norm_regression(x):
     return regression(x) / snorm, snorm
 
 
-def norm_regression_adjoint(x, gout):
-    """gx_d = gout * (d - out * sgn(x_d)) / s;  gout * d / eps where the norm is clamped"""
+def norm_regression_adjoint(x, gout, sign=None):
+    """gx_d = gout * (d - out * sgn(x_d)) / s;  gout * d / eps where the norm is clamped.  sign: used in place of sgn(x) (a
+    caller whose x is itself a computed quantity, and who knows where float64 cannot decide its sign for fp32)"""
     x, gout = _f64(x), _f64(gout)
     s = np.abs(x).sum(1)
     out, sden = norm_regression(x)
     ov = np.where(s < EPS, 0.0, out)
-    return gout[:, None] * (_disp(x.shape[1]) - ov[:, None] * sgn(x)) / sden[:, None]
+    return gout[:, None] * (_disp(x.shape[1]) - ov[:, None] * (sgn(x) if sign is None else _f64(sign))) / sden[:, None]
 
 
 # ---- Softmin(dim=1) ----------------------------------------------------------------------------------------------------------

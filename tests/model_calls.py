@@ -11,7 +11,7 @@ the data, so they are applied here to the tensors a model run really hands to ea
 
 `recording` wraps forward / backward of a list of autograd Functions (and plain launch functions) for its duration and keeps
 one `Record` per call: kind, arguments (host copies of the tensors, cloned BEFORE the call), outputs, incoming and returned
-gradients, SgaFunction's saved A / mask / kp, and every input that was written.  `check_all(records, oracle)` runs each
+gradients, SgaFunction's saved A / mask / kp, LgaRegressFunction's saved y / snorm, and every input that was written.  `check_all(records, oracle)` runs each
 record through the checker of its kind and FAILS, naming the kinds, if a recorded call has none: no op call of a model run
 goes unexamined.
 
@@ -23,7 +23,19 @@ Absolute bars of the case tables (misc_cases: `atol`) belong to data of magnitud
 error of an fp32 operation scales with its data, down as well as up -- an absolute bar below one ulp of the data cannot be
 met by any fp32 code, and one far above the data checks nothing -- so on recorded data the bar becomes
 atol * max |float64 result| of that output (`_atol`).  The regressions' outputs are in disparity units: their 1e-4 was set for
-disparities up to 192 and becomes 1e-4 * (D - 1) / 192 (`_atol_px`).  The relative parts (`rtol`) stay as they are."""
+disparities up to 192 and becomes 1e-4 * (D - 1) / 192 (`_atol_px`).  The relative parts (`rtol`) stay as they are.
+
+Non-smooth points.  A reference may apply a sign, a threshold or a selection to an EXACT input, never to a quantity the op
+computed itself: there float64 and a correct fp32 evaluation can land on different sides, and the two results differ by far
+more than any rounding bar.  The checkers were read for this.  check_lga_regress had it -- sgn(y) of the pass's own fp32 y,
+taken from the float64 y -- and now takes the call's sign where float64 cannot decide (its docstring).  The others do not:
+NormDisparityRegression, L1NormalizeGroups and their adjoints take sgn of the recorded input, and their clamp at eps = 1e-12 acts
+on a sum of |inputs| that model data only reach as an exact zero; ResidualRelu and BnApply take the ReLU mask of the backward from
+the call's own y, and hold the forward's zero set only outside the bar; BnRelu has `undecided` with the call's mask; SGA's
+arg-max is the oracle's, held by equality, and float64 is evaluated on those selections; the losses' thresholds act on
+fl32(p - t), one defined rounding of exact inputs that both sides perform alike; Softmin, the regressions, the cost volume
+and the convolution are smooth or linear; trilinear interpolation is continuous across its cell boundaries (the weight of the
+cell that changes is 0 there), and its reference is ATen's own fp32 index arithmetic."""
 import collections
 import contextlib
 import inspect
@@ -114,6 +126,8 @@ def _wrap_function(patch, records, cls):
         elif kind == "SgaFunction":
             tmp, mask = ctx.saved_tensors[5:7]
             r.saved = {"tmp": _host(tmp), "mask": _host(mask)}
+        elif kind == "LgaRegressFunction":             # the pass's own volume and norm: the call's signs (check_lga_regress)
+            r.saved = {"y": _host(ctx.saved_tensors[2]), "snorm": _host(ctx.saved_tensors[4])}
         # (between forward and backward other ops may legitimately write an input -- BatchNorm's running statistics on the
         # next call of a shared module -- so the backward is compared with what it found, not with the forward's clones)
         before = [_host(t) for t in r.live]
@@ -498,30 +512,111 @@ def check_trilinear(r, oracle=None):
     return q
 
 
-def check_lga_regress(r, oracle=None):
+UNDECIDED_CAP = 4.8e-4        # check_lga_regress: four times the largest share of undecided elements measured on stand-in data
+
+
+def check_lga_regress(r, oracle=None, planted=None):
     """One LGA pass y = LGA(x, f), then out = sum_d d y_d / max(sum_d |y_d|, eps).  Bars composed of the two ops' own:
       out       misc_cases' bar of the normalised regression (rtol 1e-5, atol' in disparity units) on the float64 pass, PLUS what
                 the pass's own roundings do to it: to first order sum_d |d - out sgn(y_d)| / s * E_y, E_y = FACTOR x chain_bound
                 (y is signed -- filters are -- so sum_d d y_d cancels, and E_y / s is not small against 1e-5)
-      backward  gy = the float64 adjoint of the regression, held by ITS bar (rtol 1e-4, atol' as everywhere); the LGA pass
+      backward  gy = the float64 adjoint of the regression, held by ITS bar (rtol 1e-4, atol' as everywhere) or, where that is
+                smaller, by what the asserted bars of out and y leave room for (derived in the code below); the LGA pass
                 behind it gets FACTOR x chain_bound for its own roundings plus that allowance on gy pushed through |f| (gx)
-                and through |taps of x| (gf), both by lga_backward on absolute values."""
+                and through |taps of x| (gf), both by lga_backward on absolute values.
+    The adjoint holds sgn(y_d), and y is a quantity the op computed ITSELF, in fp32: where |y64| <= E_y float64 cannot say which
+    sign an fp32 pass within its bound arrives at, and the two adjoints differ by 2 |go out| / s -- thousands of times the bar
+    on gy.  So, as check_bn_relu does at the ReLU's kink:
+      y         the call's own volume (saved for its backward: Record.saved) within E_y of the float64 pass.  This is what
+                entitles the call to its own sign at the elements below -- and to nothing else
+      decided   |y64| > E_y (or E_y = 0: every product is an exact zero, y64 = 0, and any fp32 sum of them is): the call's
+                sign must EQUAL float64's, else the check fails by the name "sign"
+      undecided the other elements: the reference adjoint takes the CALL's sign there, and `through` the larger of the two
+                |d -+ out| = d + |out|.  Their count is returned, and how many of them differ from float64's sign (`flipped`)
+      cap       undecided <= max(8, UNDECIDED_CAP y.size): a condition on the DATA (float64 and the bound decide it, never the
+                call's result), so that a volume that is zero or tiny everywhere is not excused wholesale.  Measured shares of
+                undecided elements: synthetic softmin volumes [2,49,48,120] at most 1.6e-5; the stand-in's LgaRegress site on
+                the CPU (tests/test_model_calls_cpu.py prints them) 12 and 14 of 225,792 at 48x96 (6.2e-5), 84 and 56 of
+                2,257,920 at 96x240x2 (3.7e-5); the same site on the inputs a device run recorded 27 of 225,792 at 48x96
+                (1.2e-4) and 63 and 85 of 2,257,920 at 96x240x2 (3.8e-5).  The stand-in's data exceed the 1e-4 first thought
+                of, so the cap is FOUR TIMES the largest measured share, 4 x 1.2e-4 = 4.8e-4.
+                planted: a mask of elements the caller PUT at the kink (tests/lga_regress_cases.py) -- all of them must be
+                undecided, and the cap then holds for the undecided elements outside the mask.
+    A record with gradients and without the saved y cannot be judged and fails."""
     x, f, radius, ndisp = r.args
+    what = repr(r)
     go = r.grad_out[0] if r.grad_in is not None else np.zeros(x.shape[:1] + x.shape[2:], np.float32)
-    y = lga_ref64.lga_forward(x, f, radius)
-    gy = m64.norm_regression_adjoint(y, go)
-    R = lga_ref64.chain_bound(x, f, gy, radius, 1)
+    y, E_y, und = lga_regress_undecided(x, f, radius)
+    if planted is not None:
+        assert und[planted].all(), (what, "planted elements that float64 decides", int((planted & ~und).sum()))
+    stray = int((und & ~planted).sum()) if planted is not None else int(und.sum())
+    assert stray <= max(8, UNDECIDED_CAP * y.size), (what, f"{stray} of {y.size} elements undecided: the data sit at the kink, not the call")
+    q = {"undecided": float(und.sum())}
+    sign = np.sign(y)
+    if "y" in r.saved:
+        yc = r.saved["y"].astype(np.float64)
+        wrong = ~und & (np.sign(yc) != sign)
+        assert not wrong.any(), (what, "sign", f"{int(wrong.sum())} decided elements, the first at {tuple(np.argwhere(wrong)[0])}")
+        q["y"] = _within("y", r.saved["y"], y, E_y)
+        q["flipped"] = float((und & (np.sign(yc) != sign)).sum())
+        sign = np.where(und, np.sign(yc), sign)
+    else:
+        assert r.grad_in is None, (what, "a call with gradients must keep its own y (Record.saved)")
+    gy = m64.norm_regression_adjoint(y, go, sign)
     out, s = m64.norm_regression(y)
     D = x.shape[1]
     d = np.arange(D, dtype=np.float64).reshape(1, D, 1, 1)
-    through = (np.abs(d - out[:, None] * np.sign(y)) * FACTOR * R["y"]).sum(1) / s
-    q = {"out": _within("out", r.outputs[0], out, 1e-5 * np.abs(out) + _atol_px(1e-4, D) + through)}
+    lever = np.where(und, d + np.abs(out[:, None]), np.abs(d - out[:, None] * np.sign(y)))
+    through = (lever * E_y).sum(1) / s
+    bar_out = 1e-5 * np.abs(out) + _atol_px(1e-4, D) + through
+    q["out"] = _within("out", r.outputs[0], out, bar_out)
     if r.grad_in is not None:
+        R = lga_ref64.chain_bound(x, f, gy, radius, 1)
         e_gy = 1e-4 * np.abs(gy) + _atol(1e-4, gy)
+        # The table's atol' is 1e-4 of the LARGEST |gy| of the volume -- a pixel whose norm is small -- granted to every element:
+        # on the stand-in's data it hides a relative error of 2^-12 in gx and gf (tests/test_model_calls_cpu.py).  What the
+        # call's gy can differ by is known from what has been asserted above: gy = go (d - out sgn) / s in three roundings,
+        # on the call's out (within bar_out of float64's) and on its norm s = sum |y_d| (each y_d within E_y, D - 1 additions):
+        #   |d gy| <= FACTOR (3 u + gamma_D) |gy| + |go| bar_out / s + |gy| sum_d E_y / s.
+        # The allowance is the smaller of the two, element by element, so no element's bar is wider than it was; where the
+        # norm is clamped (s = eps exactly, in any arithmetic) the table's stays.
+        derived = FACTOR * (3 * U + _gamma(D)) * np.abs(gy) + (np.abs(go) * bar_out / s)[:, None] + np.abs(gy) * (E_y.sum(1) / s)[:, None]
+        e_gy = np.where((np.abs(y).sum(1) < m64.EPS)[:, None], e_gy, np.minimum(e_gy, derived))
         extra = lga_ref64.lga_backward(np.abs(x), np.abs(f), e_gy, radius)
         for k, i in (("gx", 0), ("gf", 1)):
-            q[k] = _within(k, r.grad_in[i], R["want"][k], FACTOR * R[k] + extra[i])
+            bar = FACTOR * R[k] + extra[i]
+            try:
+                q[k] = _within(k, r.grad_in[i], R["want"][k], bar)
+            except AssertionError as e:
+                raise AssertionError(*e.args, _lga_regress_element(k, r.grad_in[i], R["want"][k], bar, y, r.saved["y"], E_y, und, radius)) from None
     return q
+
+
+def lga_regress_undecided(x, f, radius):
+    """-> (the float64 pass y, E_y = FACTOR x chain_bound's bound of it, the mask of elements whose sign float64 cannot decide
+    for an fp32 pass: |y| <= E_y, where E_y > 0)"""
+    R = lga_ref64.chain_bound(x, f, None, radius, 1, backward=False)
+    y, E_y = R["want"]["y"], FACTOR * R["y"]
+    return y, E_y, (np.abs(y) <= E_y) & (E_y > 0)
+
+
+def _lga_regress_element(k, got, want, bar, y, y_call, E_y, und, radius):
+    """what a failure of gx / gf is to be explained from: the element with the largest error / bar, and the y that its
+    adjoint reads -- gx[b,d,i,j]: the taps' readers, d +- 1, i +- r, j +- r; gf[b,t,i,j]: the column of its pixel"""
+    err = np.abs(got.astype(np.float64) - want)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        idx = np.unravel_index(np.argmax(np.where(err == 0, 0.0, err / bar)), err.shape)
+    b, c, i, j = (int(v) for v in idx)
+    D, H, W = y.shape[1:]
+    if k == "gx":
+        win = (b, slice(max(c - 1, 0), min(c + 2, D)), slice(max(i - radius, 0), min(i + radius + 1, H)), slice(max(j - radius, 0), min(j + radius + 1, W)))
+    else:
+        win = (b, slice(None), i, j)
+    lines = [f"{k}{list(idx)}: got {got[idx]!r} float64 {want[idx]!r} bar {bar[idx]:.3g}; y it reads (float64 / the call's / E_y / undecided):"]
+    order = np.argsort((np.abs(y[win]) / np.maximum(E_y[win], 1e-300)).ravel())[:6]
+    for o in order:
+        lines.append(f"  {y[win].ravel()[o]!r} / {y_call[win].ravel()[o]!r} / {E_y[win].ravel()[o]:.3g} / {bool(und[win].ravel()[o])}")
+    return "\n".join(lines)
 
 
 def _relu_adjoint(r, y, scale, i_t, i_rem):
@@ -576,10 +671,11 @@ def check_bn_apply(r, oracle=None):
     return q
 
 
-def check_bn_relu(r, oracle=None):
+def check_bn_relu(r, oracle=None, enforce=True):
     """bn_cases.check on the recorded tensors: a Case built around them (nothing generated, nothing nudged).  Recorded data
     cannot be nudged away from the ReLU's kink, so at the elements that float64 cannot decide for fp32 (|z| <= 4 B_y) the
-    mask is the call's own y > 0; everywhere else float64 decides (bn_ref64.Reference, relu_positive)."""
+    mask is the call's own y > 0; everywhere else float64 decides (bn_ref64.Reference, relu_positive).  enforce=False: a
+    measurement (of ATen's chain), nothing is asserted."""
     x, rem, weight, bias, rmean, rvar, momentum, eps, relu = r.args
     N, C = x.shape[:2]
     shape = (N, C, x.size // (N * C))
@@ -601,7 +697,7 @@ def check_bn_relu(r, oracle=None):
         for i, key in enumerate(("grad_x", "grad_rem", "grad_weight", "grad_bias")):
             if r.grad_in[i] is not None:
                 got[key], want[i] = (r.grad_in[i].reshape(shape) if i < 2 else r.grad_in[i]), True
-    q = bn_cases.check(c, got, want=tuple(want), verbose=False, saved=False)
+    q = bn_cases.check(c, got, want=tuple(want), verbose=False, enforce=enforce, saved=False)
     q["undecided"] = float(c.ref.undecided().sum())
     return q
 

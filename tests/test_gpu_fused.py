@@ -3,6 +3,7 @@ torch statements on the CPU (oracle/fused_ref.py; LGA/SGA through the C oracle).
 import numpy as np
 import pytest
 
+import lga_regress_cases as lrc
 import parity_cases as pc
 from oracle import fused_ref as fr
 
@@ -170,6 +171,50 @@ def test_dispagg_tail_no_grad_equals_autograd_output(torch_mod, radius):
     torch.cuda.synchronize()
     assert not without.requires_grad and np.isfinite(_np(without)).all()
     assert np.array_equal(_np(with_grad).view(np.uint32), _np(without).view(np.uint32))
+
+
+def _lga_regress_on_the_device(torch, monkeypatch):
+    """LgaRegressFunction under the recorder of tests/model_calls.py: its y and snorm are the ones its backward was given"""
+    import model_calls as M
+    from ganet_amd import _native
+    from ganet_amd.functions.fused import LgaRegressFunction
+
+    def call(x, f, go, r):
+        B, D, H, W = x.shape
+        xt, ft = torch.from_numpy(x).cuda(), torch.from_numpy(f).cuda()
+        s_abs, s_dy = torch.empty(B, H, W, device="cuda"), torch.empty(B, H, W, device="cuda")
+        try:                                           # which arm the Function takes: the entry's own answer
+            _native.lib().call("ganet_lga_forward_regress", xt.data_ptr(), ft.data_ptr(), None, s_abs.data_ptr(), s_dy.data_ptr(),
+                               B, D, H, W, r, torch.cuda.current_stream().cuda_stream)
+            fused = True
+        except _native.GanetError as e:
+            assert e.code == _native.E_UNSUPPORTED, e
+            fused = False
+        with M.recording(monkeypatch, [LgaRegressFunction]) as records:
+            if go is None:
+                with torch.no_grad():
+                    LgaRegressFunction.apply(xt, ft, r, D)
+            else:
+                LgaRegressFunction.apply(xt.requires_grad_(), ft.requires_grad_(), r, D).backward(torch.from_numpy(go).cuda())
+            torch.cuda.synchronize()
+        rec, = records
+        assert M.undeclared_writes(records) == []
+        if go is None:
+            assert rec.grad_in is None and rec.saved == {}
+            return {"out": rec.outputs[0], "fused": fused}
+        return {"out": rec.outputs[0], "y": rec.saved["y"], "snorm": rec.saved["snorm"], "gx": rec.grad_in[0], "gf": rec.grad_in[1],
+                "fused": fused}
+
+    return call
+
+
+@pytest.mark.parametrize("case", lrc.CASES, ids=lrc.case_id)
+def test_lga_regress_against_float64(torch_mod, monkeypatch, case):
+    """tests/lga_regress_cases.py, as tests/test_sim_fused.py runs it on the emulator: general values, y planted at the sign
+    kink (the deterministic form of what a model run showed now and then), a clamped norm; with and without autograd"""
+    from ganet_amd import _native
+    assert not _native.lib().is_simulator
+    lrc.run(case, _lga_regress_on_the_device(torch_mod, monkeypatch))
 
 
 def test_norm_regression_full_size(torch_mod):

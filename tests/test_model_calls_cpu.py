@@ -18,9 +18,16 @@ with the ORACLE's own results as `got`.
                two Disp and one DispAgg sites: calibration against a plain fp32 evaluation (disp_tail_ref64.Float32Model in both
                variants of lambda; a numpy fp32 accumulation of the convolution, and ATen's), and the same teeth plus every
                entry of the two MUTATIONS tables.
+  the others   every other kind of model_calls.CHECKERS -- LgaRegress, cost volume, the regressions, L1 normalise, softmin,
+               trilinear, ResidualRelu, BnApply, BnRelu, DisparityLoss, MyLoss2 -- on records built by hand from what the
+               stand-in's CPU run hands to each site (hooks; both crops): a plain fp32 statement of the op stays inside the bar
+               (by how much is printed), zeros and a factor 1 + 2^-12 on every compared array are rejected.
+  the kink     LgaRegress's sgn(y): an fp32 pass with the other sign where float64 cannot decide is accepted, the same flip
+               at decided elements is rejected, and so is every lga_ref64.MUTATIONS entry behind the regression.
   stand-in     tied to the reference where that exists: the reference's SGABlock, Disp and DispAgg and the stand-in's, with one
                state_dict, give the same bits forward and backward, and every rebinder of harness.fuse counts the same sites."""
 import collections
+import copy
 import os
 import sys
 
@@ -34,6 +41,7 @@ sys.path.insert(0, ROOT)
 import disp_conv_ref64  # noqa: E402
 import disp_tail_ref64  # noqa: E402
 import lga_ref64  # noqa: E402
+import lga_regress_cases as lrc  # noqa: E402
 import model_calls as M  # noqa: E402
 import parity_cases as pc  # noqa: E402
 import sga_ref64 as s64  # noqa: E402
@@ -48,7 +56,7 @@ MAX_DISP = 48
 CROPS = {"48x96": (48, 96, 1), "96x240x2": (96, 240, 2)}
 # SGA calls per forward (models/GANet11.py, models/GANet_deep.py; tests/standin_net.py: sga1, sga11, sga2, sga3); all call LGA2 twice
 N_SGA = {"GANet11": 4, "GANet_deep": 7, "standin": 4}
-_RUNS, _SITES = {}, {}
+_RUNS, _SITES, _OPS = {}, {}, {}
 
 
 def _ref(*values):
@@ -62,6 +70,7 @@ def _release_the_runs():
     yield
     _RUNS.clear()
     _SITES.clear()
+    _OPS.clear()
 
 
 def _recorded(oracle, name, crop):
@@ -74,20 +83,34 @@ def _recorded(oracle, name, crop):
             model = standin_net.build(MAX_DISP, "cpu")
             route_cpu_through_oracle(model, oracle)
             sites = _watch_the_disp_sites(model)
+            ops = _watch_the_op_sites(model)
         else:
             model = steps.build_model(name, MAX_DISP, "cpu", hook=lambda m: route_cpu_through_oracle(m, oracle))
         left, right, target = steps.synthetic_batch(B, H, W, MAX_DISP, "cpu")
-        with pytest.MonkeyPatch.context() as patch, M.recording(patch, *M.oracle_functions()) as records:
+        functions, plain = M.oracle_functions()
+        if name == "standin":                                       # pure tensor arithmetic: the product's own Function runs on the CPU
+            from ganet_amd.functions.GANet import MyLoss2Function
+            functions = functions + [MyLoss2Function]
+        with pytest.MonkeyPatch.context() as patch, M.recording(patch, functions, plain) as records:
             model.train()
             outs = model(left, right)
             steps.loss_mix("GANet_deep" if name == "standin" else name, outs, target, target < MAX_DISP, steps.criterion(True)).backward()
+            if name == "standin":
+                loss_record = records.pop(next(i for i, r in enumerate(records) if r.kind == "MyLoss2Function"))
             n_train = len(records)
             if name == "standin":
                 _SITES[crop] = [_site_tensors(s) for s in sites]
                 sites.clear()
+                train_ops = _op_tensors(ops)
+                ops.clear()
             steps.predict(model, left, right)
             if name == "standin":
                 _SITES[crop] += [_site_tensors(s) for s in sites]
+                _OPS[crop] = {"train": train_ops, "infer": _op_tensors(ops), "myloss2": loss_record, "target": _np32(target),
+                              "preds": [_np32(o) for o in outs]}
+                for part, recs in (("train", records[:n_train]), ("infer", records[n_train:])):
+                    _OPS[crop][part]["lga"] = [_lga_site(r) for r in recs if r.kind == "OracleLgaChain"]
+                    _OPS[crop][part]["sga"] = [_sga_site(r) for r in recs if r.kind == "OracleSga"]
         _RUNS[name, crop] = (records[:n_train], records[n_train:])
     return _RUNS[name, crop]
 
@@ -120,6 +143,75 @@ def _site_tensors(s):
     np32 = lambda t: None if t is None else np.ascontiguousarray(t.detach().numpy(), np.float32)      # noqa: E731
     return {"name": s["name"], "kind": s["kind"], "x": np32(s["x"]), "w": np32(s["w"]), "c": np32(s["c"]), "out": np32(s["out"]),
             "g_c": np32(s["c"].grad), "g_out": np32(s["out"].grad), "maxdisp": MAX_DISP}
+
+
+def _np32(t):
+    return None if t is None else np.ascontiguousarray(t.detach().numpy(), np.float32)
+
+
+def _watch_the_op_sites(model):
+    """forward hooks that keep what every OTHER op of model_calls.CHECKERS would be handed at its site in the stand-in (the
+    inputs, cloned when they are met, and the gradient that later arrives at the site's output): the cost volume, the raw
+    guidance and filter maps in front of the L1 normalisations, every BatchNorm (+ residual) (+ ReLU) site -- BasicConv, and
+    the SGABlocks' tails with their residual.  -> the dict the calls are appended to"""
+    ops = collections.defaultdict(list)
+    met = {}
+
+    def keep_grad(t, d):
+        d["g"] = None
+        if t.requires_grad:
+            t.register_hook(lambda g: d.__setitem__("g", g.detach().clone()))
+
+    def cv_hook(mod, args, out):
+        d = {"x": args[0].detach().clone(), "y": args[1].detach().clone(), "Dn": out.shape[2]}
+        keep_grad(out, d)
+        ops["cv"].append(d)
+
+    def bn_pre(mod, args):
+        met[mod] = {"x": args[0].detach().clone(), "weight": mod.weight.detach().clone(), "bias": mod.bias.detach().clone(),
+                    "running_mean": mod.running_mean.clone(), "running_var": mod.running_var.clone(), "momentum": mod.momentum,
+                    "eps": mod.eps, "training": mod.training}
+
+    def conv_hook(mod, args, out, name):
+        d = {**met.pop(mod.bn), "name": name, "rem": None, "relu": bool(mod.relu)}
+        keep_grad(out, d)
+        ops["bn"].append(d)
+
+    def block_hook(mod, args, out, name):
+        d = {**met.pop(mod.conv_refine.bn if mod.refine else mod.bn), "name": name, "rem": args[0].detach().clone(), "relu": True}
+        keep_grad(out, d)
+        ops["bn"].append(d)
+
+    model.cv.register_forward_hook(cv_hook)
+    for key, conv in list(model.weight_sg.items()) + list(model.weight_lg.items()):
+        conv.register_forward_hook(lambda mod, args, out, key=key: ops["raw"].append({"key": key, "x": out.detach().clone()}))
+    refines = {m.conv_refine for m in model.modules() if type(m).__name__ == "SGABlock" and m.refine}
+    for name, m in model.named_modules():
+        if isinstance(m, torch.nn.modules.batchnorm._BatchNorm):
+            m.register_forward_pre_hook(bn_pre)
+        if type(m).__name__ == "BasicConv" and m.use_bn and m not in refines:
+            m.register_forward_hook(lambda mod, args, out, name=name: conv_hook(mod, args, out, name))
+        elif type(m).__name__ == "SGABlock":
+            m.register_forward_hook(lambda mod, args, out, name=name: block_hook(mod, args, out, name))
+    return ops
+
+
+def _op_tensors(ops):
+    """host copies of what _watch_the_op_sites has kept so far (after the backward: the gradients have arrived)"""
+    conv = lambda v: _np32(v) if isinstance(v, torch.Tensor) else v      # noqa: E731
+    return {k: [{kk: conv(v) for kk, v in d.items()} for d in calls] for k, calls in ops.items()}
+
+
+def _lga_site(r):
+    x, f, radius, passes = M._lga_inputs(r)
+    g = r.grad_in is not None
+    return {"x": x, "f": f, "radius": radius, "passes": passes, "y": r.outputs[0], "gy": r.grad_out[0] if g else None,
+            "gx": r.grad_in[1] if g else None, "gf": r.grad_in[2] if g else None}
+
+
+def _sga_site(r):
+    """the four normalised guidance volumes an SGA call got and the gradients it returned for them"""
+    return {"ks": list(r.args[2:6]), "gks": list(r.grad_in[2:6]) if r.grad_in is not None else None}
 
 
 @pytest.mark.parametrize("name,crop", [_ref("GANet11", "48x96"), _ref("GANet_deep", "48x96"), _ref("GANet_deep", "96x240x2"),
@@ -306,6 +398,8 @@ def _conv_record(site, how):
 
 
 def _sites(oracle, crop="48x96"):
+    if crop not in _SITES:
+        _RUNS.pop(("standin", crop), None)
     _recorded(oracle, "standin", crop)
     return _SITES[crop]
 
@@ -333,8 +427,6 @@ def test_plain_fp32_stays_inside_the_bars_of_the_disp_tail_and_the_disp_conv(por
                     worst["DispTail " + variant, k] = max(worst.get(("DispTail " + variant, k), 0.0), v)
     print(f"stand-in {crop}: plain fp32 against the float64 statements, largest error / bar (bar: 1)\n" + M.fmt(worst))
     assert {k for _, k in worst} == {"y", "grad_x", "grad_weight", "out"} and max(worst.values()) <= 1.0
-    if crop != "48x96":
-        del _SITES[crop]
 
 
 def test_every_disp_tail_record_rejects_a_wrong_result(port_oracle):
@@ -394,8 +486,428 @@ def test_every_disp_conv_record_rejects_a_wrong_result(port_oracle):
     assert all(exercised.values()), exercised
 
 
+# ---- every other checker of model_calls.CHECKERS, on the stand-in's sites --------------------------------------------------------
+# Records built by hand, as above: the inputs and the incoming gradient are what the stand-in's CPU run hands to the site, the
+# results are a PLAIN fp32 statement of the op -- numpy with every intermediate float32, or ATen on the CPU where the op is
+# ATen's own chain (softmin, trilinear, batch_norm) -- never the device's or the emulator's.  A checker whose bar plain fp32
+# cannot meet is too tight and fails a correct kernel now and then; one that accepts zeros or a 2^-12 error checks nothing.
+F32 = np.float32
+OTHER_KINDS = ("LgaRegressFunction", "GetCostVolumeFunction", "DisparityRegressionFunction", "L1NormalizeGroupsFunction",
+               "NormDisparityRegressionFunction", "SoftminFunction", "SoftminDisparityRegressionFunction", "TrilinearUpsampleFunction",
+               "ResidualReluFunction", "BnApplyFunction", "BnReluFunction", "DisparityLossFunction", "MyLoss2Function")
+COUNTS = ("undecided", "flipped")                       # keys of a checker's dict that are counts, not error / bar
+
+
+def _ops(oracle, crop="48x96"):
+    if crop not in _OPS or crop not in _SITES:
+        _RUNS.pop(("standin", crop), None)
+        _recorded(oracle, "standin", crop)
+    return _OPS[crop], _SITES[crop]
+
+
+def _t(a):
+    return torch.from_numpy(np.ascontiguousarray(a))
+
+
+def _disp32(D):
+    return np.arange(D, dtype=F32).reshape(1, D, 1, 1)
+
+
+def _cost_volume_record(s):
+    x, y, Dn, g = s["x"], s["y"], s["Dn"], s["g"]
+    N, C, H, W = x.shape
+    cost = np.zeros((N, 2 * C, Dn, H, W), F32)
+    for i in range(min(Dn, W)):
+        cost[:, :C, i, :, i:], cost[:, C:, i, :, i:] = x[..., i:], y[..., :W - i]
+    if g is None:
+        return _record("GetCostVolumeFunction", [x, y, Dn], [cost])
+    gx, gy = np.zeros_like(x), np.zeros_like(y)
+    for i in range(min(Dn, W)):                          # one fp32 addition per plane, in order
+        gx[..., i:] += g[:, :C, i, :, i:]
+        gy[..., :W - i] += g[:, C:, i, :, i:]
+    return _record("GetCostVolumeFunction", [x, y, Dn], [cost], [g], [gx, gy, None])
+
+
+def _regression_record(x, go):
+    D = x.shape[1]
+    out = (x * _disp32(D)).sum(1, dtype=F32)
+    if go is None:
+        return _record("DisparityRegressionFunction", [x, D], [out])
+    return _record("DisparityRegressionFunction", [x, D], [out], [go], [go[:, None] * _disp32(D), None])
+
+
+def _l1_record(x, G, C, K, gys):
+    N, _, H, W = x.shape
+    x6 = x.reshape(N, G, C, K, H, W)
+    s = np.maximum(np.abs(x6).sum(3, keepdims=True, dtype=F32), F32(1e-12))
+    y = x6 / s
+    outs = [np.ascontiguousarray(y[:, g]) for g in range(G)]
+    if gys is None:
+        return _record("L1NormalizeGroupsFunction", [x, G, C, K], outs)
+    gy = np.stack([g.reshape(N, C, K, H, W) for g in gys], 1)
+    dot = (gy * y).sum(3, keepdims=True, dtype=F32)
+    gx = ((gy - np.sign(x6) * dot) / s).astype(F32)
+    return _record("L1NormalizeGroupsFunction", [x, G, C, K], outs, [g.reshape(N, C, K, H, W) for g in gys], [gx.reshape(x.shape), None, None, None])
+
+
+def _norm_regression_record(x, go):
+    D = x.shape[1]
+    s = np.maximum(np.abs(x).sum(1, dtype=F32), F32(1e-12))
+    out = (x * _disp32(D)).sum(1, dtype=F32) / s
+    if go is None:
+        return _record("NormDisparityRegressionFunction", [x, D], [out])
+    gx = (go[:, None] * ((_disp32(D) - out[:, None] * np.sign(x)) / s[:, None])).astype(F32)
+    return _record("NormDisparityRegressionFunction", [x, D], [out], [go], [gx, None])
+
+
+def _softmin_record(x, gy):
+    xt = _t(x).requires_grad_(gy is not None)
+    y = torch.nn.functional.softmin(xt, dim=1)
+    if gy is None:
+        return _record("SoftminFunction", [x], [_np32(y)])
+    return _record("SoftminFunction", [x], [_np32(y)], [gy], [_np32(torch.autograd.grad(y, xt, _t(gy))[0])])
+
+
+def _softmin_regression_record(x, go):
+    D = x.shape[1]
+    xt = _t(x).requires_grad_()
+    out = (torch.nn.functional.softmin(xt, dim=1) * _t(_disp32(D))).sum(1)
+    return _record("SoftminDisparityRegressionFunction", [x, D], [_np32(out)], [go], [_np32(torch.autograd.grad(out, xt, _t(go))[0]), None])
+
+
+def _upsampled(site, go=None):
+    """the trilinear output of a Disp / DispAgg site (ATen, fp32) and, for a Disp, the gradient Softmin + regression hands back
+    to it for the site's incoming `go`"""
+    u = torch.nn.functional.interpolate(_t(site["c"]), list(_size(site)), mode="trilinear", align_corners=False)[:, 0]
+    if go is None:
+        return _np32(u), None
+    u.requires_grad_()
+    out = (torch.nn.functional.softmin(u, dim=1) * _t(_disp32(u.shape[1]))).sum(1)
+    return _np32(u), _np32(torch.autograd.grad(out, u, _t(go))[0])
+
+
+def _trilinear_record(site, gu):
+    from misc_cases import _aten_trilinear
+    x, size = site["c"], _size(site)
+    if gu is None:
+        y, _ = _aten_trilinear(x, np.zeros(x.shape[:2] + size, F32), size)
+        return _record("TrilinearUpsampleFunction", [x, size], [y])
+    y, gx = _aten_trilinear(x, np.ascontiguousarray(gu[:, None]), size)
+    return _record("TrilinearUpsampleFunction", [x, size], [y], [np.ascontiguousarray(gu[:, None])], [gx, None])
+
+
+def _folded(s):
+    scale = (s["weight"].astype(F32) / np.sqrt(s["running_var"] + F32(s["eps"]), dtype=F32)).astype(F32)
+    return scale, (s["bias"] - s["running_mean"] * scale).astype(F32)
+
+
+def _affine_relu32(x, rem, scale, shift, relu):
+    C = x.shape[1]
+    b = lambda v: v.reshape((1, C) + (1,) * (x.ndim - 2))      # noqa: E731
+    y = x if scale is None else b(scale) * x + b(shift)
+    y = y if rem is None else y + rem
+    assert y.dtype == F32
+    return np.maximum(y, F32(0)) if relu else y
+
+
+def _relu_grads32(y, gy, scale, relu):
+    g = np.where(y > 0, gy, F32(0)) if relu else gy
+    C = y.shape[1]
+    return (g if scale is None else scale.reshape((1, C) + (1,) * (y.ndim - 2)) * g), g
+
+
+def _bn_aten(s):
+    """y and the four gradients of relu(batch_norm(x) [+ rem]) with batch statistics by ATen on the CPU, and the running
+    statistics it leaves"""
+    x, w, b = (_t(s[k]).requires_grad_() for k in ("x", "weight", "bias"))
+    rem = None if s["rem"] is None else _t(s["rem"]).requires_grad_()
+    rm, rv = _t(s["running_mean"].copy()), _t(s["running_var"].copy())
+    y = torch.nn.functional.batch_norm(x, rm, rv, w, b, True, s["momentum"], s["eps"])
+    y = y if rem is None else y + rem
+    y = torch.relu(y) if s["relu"] else y
+    leaves = [x, w, b] + ([rem] if rem is not None else [])
+    gs = [_np32(g) for g in torch.autograd.grad(y, leaves, _t(s["g"]))]
+    return _np32(y), gs[0], (gs[3] if rem is not None else None), gs[1], gs[2], _np32(rm), _np32(rv)
+
+
+def _bn_model(s):
+    """the same by bn_ref64.Float32Model: fp32 element by element, the per-channel sums in fp64 -- the arithmetic BnRelu's bars
+    are derived for (ATen's fp32 sums do not reach them: measured, not asserted, in the calibration below)"""
+    import bn_ref64
+    N, C = s["x"].shape[:2]
+    flat = lambda a: None if a is None else a.reshape(N, C, -1)      # noqa: E731
+    m = bn_ref64.Float32Model(flat(s["x"]), flat(s["rem"]), flat(s["g"]), s["weight"], s["bias"], s["running_mean"], s["running_var"],
+                              s["momentum"], s["eps"], s["relu"])
+    shaped = lambda a: np.ascontiguousarray(a, F32).reshape(s["x"].shape)      # noqa: E731
+    return (shaped(m.y), shaped(m.grad_x), shaped(m.grad_rem) if s["rem"] is not None else None, m.grad_weight, m.grad_bias,
+            m.running_mean, m.running_var)
+
+
+def _bn_relu_record(s, how="model"):
+    y, gx, grem, gw, gb, rm, rv = (_bn_model if how == "model" else _bn_aten)(s)
+    r = _record("BnReluFunction", [s["x"], s["rem"], s["weight"], s["bias"], s["running_mean"], s["running_var"], s["momentum"],
+                                   s["eps"], s["relu"]], [y], [s["g"]], [gx, grem, gw, gb] + [None] * 5)
+    r.after = {4: rm, 5: rv}
+    return r
+
+
+def _bn_apply_record(s, gy=None):
+    scale, shift = _folded(s)
+    y = _affine_relu32(s["x"], s["rem"], scale, shift, s["relu"])
+    args = [s["x"], s["rem"], scale, shift, s["relu"], False]
+    if gy is None:
+        return _record("BnApplyFunction", args, [y])
+    g_x, g_rem = _relu_grads32(y, gy, scale, s["relu"])
+    return _record("BnApplyFunction", args, [y], [gy], [g_x, g_rem if s["rem"] is not None else None, None, None, None, None])
+
+
+def _residual_relu_record(s, folded, gy=None):
+    """an SGABlock's tail as ResidualReluFunction sees it: eval -- the BatchNorm folded; training -- relu(t + rem) on the
+    framework's t = bn(.)"""
+    if folded:
+        t, (scale, shift) = s["x"], _folded(s)
+    else:
+        xt = _t(s["x"])
+        t = _np32(torch.nn.functional.batch_norm(xt, _t(s["running_mean"].copy()), _t(s["running_var"].copy()), _t(s["weight"]), _t(s["bias"]),
+                                                 True, s["momentum"], s["eps"]))
+        scale = shift = None
+    y = _affine_relu32(t, s["rem"], scale, shift, True)
+    args = [t, s["rem"], scale, shift, False]
+    if gy is None:
+        return _record("ResidualReluFunction", args, [y])
+    g_t, g_rem = _relu_grads32(y, gy, scale, True)
+    return _record("ResidualReluFunction", args, [y], [gy], [g_t, g_rem, None, None, None])
+
+
+def _rho32(v, kind, thresh=3, alpha=2):
+    """loss_ref64.rho64 with every constant and operation fp32"""
+    assert v.dtype == F32
+    if kind == 0:
+        return np.where(v < 1, F32(0.5) * v * v, v - F32(0.5))
+    knee, span, far = F32(thresh), F32(alpha), F32(thresh) + F32(alpha)
+    v = np.where(v < knee, v * v / knee, v)
+    v = np.where((v >= knee) & (v <= far), F32(2) * v - (v - knee) ** 2 / (F32(2) * span) - knee, v)
+    return np.where(v > far, v + span / F32(2), v).astype(F32)
+
+
+def _disparity_loss_record(preds, target):
+    """the fused criterion of the stand-in's training step (DisparityLoss.for_model("GANet_deep", MAX_DISP)): sums and means in
+    fp32 numpy; the gradients by loss_ref64's own float32 statement -- the checker asks for its bits"""
+    import loss_cases
+    import loss_ref64
+    from ganet_amd.modules.fused import DisparityLoss
+    crit = DisparityLoss.for_model("GANet_deep", MAX_DISP)
+    params = np.asarray(crit.values, F32)
+    p = dict(zip(loss_ref64.PARAMS, params))
+    ok = loss_ref64.valid(target, p["hi"], p["lo"], crit.mask_mode)
+    n = F32(ok.sum())
+    stats, loss = [n], F32(0)
+    for k, (q, kind) in enumerate(zip(preds, crit.kinds)):
+        v = np.abs(q - target)[ok]
+        mean_rho = _rho32(v, kind, p["thresh"], p["alpha"]).sum(dtype=F32) / n
+        stats += [mean_rho, v.sum(dtype=F32) / n, F32((v > p["rate"]).sum()) / n]
+        loss = loss + p[f"w{k}"] * mean_rho
+    c = loss_cases.Case("stand-in", target.shape, preds, target, crit.kinds, [p["w0"], p["w1"], p["w2"]], thresh=p["thresh"], alpha=p["alpha"],
+                        mask_mode=crit.mask_mode, hi=p["hi"], lo=p["lo"], rate=p["rate"])
+    grads = c.ref.grads(1.0, np.float32)
+    return _record("DisparityLossFunction", [target, params, None, crit.kinds, crit.mask_mode] + list(preds), [np.asarray(loss, F32), np.asarray(stats, F32)],
+                   [np.asarray(1.0, F32), None], [None] * 5 + grads)
+
+
+def _lga_regress_site(ops, sites, part, oracle):
+    """x: the first pass of the second LGA2 (the oracle's fp32) on the Softmin output, f: its filters, go: what arrives at the
+    DispAgg's output"""
+    lga = ops[part]["lga"][1]
+    x = oracle.lga_forward(lga["x"], lga["f"], lga["radius"])
+    go = next(s for s in sites if s["kind"] == "DispAgg" and (s["g_out"] is not None) == (part == "train"))["g_out"]
+    return x, lga["f"], lga["radius"], go
+
+
+def _lga_regress_record(x, f, r, go, y=None):
+    return lrc.record(x, f, r, lrc.regress32(x, f, go, r, y), go)
+
+
+def _other_records(oracle, crop, aten=None):
+    """[(what, Record)] for every kind of OTHER_KINDS, training sites (with gradients) and steps.predict's (without).  aten: a
+    list that gets the BnRelu records with ATen's results (measured only)"""
+    ops, sites = _ops(oracle, crop)
+    res, aten = [], [] if aten is None else aten
+    add = lambda what, r: res.append((what, r))      # noqa: E731
+    dispagg = {part: next(s for s in sites if s["kind"] == "DispAgg" and (s["g_out"] is not None) == (part == "train")) for part in ("train", "infer")}
+    disps = [s for s in sites if s["kind"] == "Disp"]
+    for part in ("train", "infer"):
+        o, go = ops[part], dispagg[part]["g_out"]
+        add(f"LgaRegress {part}", _lga_regress_record(*_lga_regress_site(ops, sites, part, oracle)))
+        add(f"cost volume {part}", _cost_volume_record(o["cv"][0]))
+        lga1, lga2 = o["lga"]
+        add(f"softmin {part}", _softmin_record(lga1["y"], lga2["gx"]))
+        add(f"normalised regression {part}", _norm_regression_record(lga2["y"], go))
+        add(f"regression DispAgg {part}", _regression_record(_np32(torch.nn.functional.normalize(_t(lga2["y"]), p=1, dim=1)), go))
+        add(f"trilinear DispAgg {part}", _trilinear_record(dispagg[part], lga1["gx"]))
+        # the raw maps are the same in both passes' order: sg1, sg2, sg3, sg11, lg1, lg2 (ModuleDict); the SGA calls: sga1, sga11, sga2, sga3
+        raw = {d["key"]: d["x"] for d in o["raw"]}
+        for key, sga in zip(("sg1", "sg11", "sg2", "sg3"), o["sga"]):
+            C = sga["ks"][0].shape[1]
+            r = _l1_record(raw[key], 4, C, 5, sga["gks"])
+            assert all(np.allclose(a, b, rtol=1e-6, atol=0) for a, b in zip(r.outputs, sga["ks"])), (key, "not this SGA call's guidance")
+            add(f"L1 normalise {key} {part}", r)
+        for key, lga in zip(("lg1", "lg2"), o["lga"]):
+            r = _l1_record(raw[key], 1, 1, 75, None if lga["gf"] is None else [lga["gf"]])
+            assert np.allclose(r.outputs[0][:, 0], lga["f"], rtol=1e-6, atol=0), (key, "not this LGA call's filters")
+            add(f"L1 normalise {key} {part}", r)
+    for k, s in enumerate(disps):
+        u, gu = _upsampled(s, s["g_out"])
+        add(f"softmin + regression Disp{k}", _softmin_regression_record(u, s["g_out"]))
+        add(f"regression Disp{k}", _regression_record(_np32(torch.nn.functional.softmin(_t(u), dim=1)), s["g_out"]))
+        add(f"trilinear Disp{k}", _trilinear_record(s, gu))
+    train_bn, infer_bn = ops["train"]["bn"], ops["infer"]["bn"]
+    assert [s["name"] for s in train_bn] == [s["name"] for s in infer_bn] and len(train_bn) == 13 + 4
+    assert all(s["training"] and s["g"] is not None for s in train_bn) and not any(s["training"] or s["g"] is not None for s in infer_bn)
+    for s, e in zip(train_bn, infer_bn):
+        add(f"BnRelu {s['name']}", _bn_relu_record(s))
+        aten.append((f"BnRelu {s['name']} by ATen", _bn_relu_record(s, "aten")))
+        add(f"BnApply {e['name']}", _bn_apply_record(e))
+        add(f"BnApply {e['name']} + the training step's gradient", _bn_apply_record(e, s["g"]))
+        if s["rem"] is not None:
+            add(f"ResidualRelu {s['name']} training", _residual_relu_record(s, False, s["g"]))
+            add(f"ResidualRelu {e['name']} folded", _residual_relu_record(e, True))
+            add(f"ResidualRelu {e['name']} folded + the training step's gradient", _residual_relu_record(e, True, s["g"]))
+    add("DisparityLoss", _disparity_loss_record(_OPS[crop]["preds"], _OPS[crop]["target"]))
+    add("MyLoss2", _OPS[crop]["myloss2"])
+    assert {r.kind for _, r in res} == set(OTHER_KINDS)
+    return res
+
+
+@pytest.mark.parametrize("crop", ["48x96", "96x240x2"])
+def test_plain_fp32_stays_inside_the_bars_of_every_other_checker(port_oracle, crop):
+    """calibration, per kind of OTHER_KINDS: the plain fp32 statement is accepted, and the largest error / bar per kind and key
+    is printed (profiles/r17a_checker_calibration.txt keeps the figures).  A kind above 0.5 of its bar is named: its bar leaves
+    a correct kernel little room.  LgaRegress: the share of undecided elements on the stand-in's data, which the checker's
+    cap is set from."""
+    worst, report, aten = collections.OrderedDict(), [], []
+    for what, r in _other_records(port_oracle, crop, aten):
+        q = M.CHECKERS[r.kind](r, port_oracle)
+        report.append(f"{what:60s} {r!r}: " + " ".join(f"{k}={v:.3g}" for k, v in q.items()))
+        for k, v in q.items():
+            worst[r.kind, k] = max(worst.get((r.kind, k), 0.0), v)
+        if r.kind == "LgaRegressFunction":
+            print(f"stand-in {crop} {what}: {int(q['undecided'])} of {r.args[0].size} elements undecided, share {q['undecided'] / r.args[0].size:.3g}")
+    print("\n".join(report))
+    print(f"stand-in {crop}: plain fp32 against the float64 statements, largest error / bar (bar: 1)\n" + M.fmt(worst))
+    stock = {}
+    for what, r in aten:
+        for k, v in M.check_bn_relu(r, enforce=False).items():
+            stock[k] = max(stock.get(k, 0.0), v)
+    print("BnRelu by ATen's batch_norm (fp32 sums; measured, not asserted):", {k: round(v, 3) for k, v in stock.items() if k not in COUNTS})
+    ratios = {k: v for k, v in worst.items() if k[1] not in COUNTS}
+    print("above half of the bar:", {k: round(v, 3) for k, v in ratios.items() if v > 0.5})
+    assert {k for k, _ in worst} == set(OTHER_KINDS) and max(ratios.values()) <= 1.0
+    if crop != "48x96":                                             # nobody else uses the large crop
+        del _OPS[crop], _SITES[crop]
+
+
+def _slots(r):
+    """every array of a record that its checker compares: (attribute, index)"""
+    slots = [("outputs", i) for i, o in enumerate(r.outputs) if isinstance(o, np.ndarray)]
+    if r.grad_in is not None:
+        slots += [("grad_in", i) for i, g in enumerate(r.grad_in) if g is not None]
+    slots += [("after", i) for i in r.after] + [("saved", k) for k in r.saved if k != "snorm"]      # (snorm is kept, not compared)
+    return slots
+
+
+def _spoilt(r, slot, fn):
+    attr, i = slot
+    s = copy.copy(r)
+    held = copy.copy(getattr(r, attr))
+    held[i] = fn(held[i])
+    setattr(s, attr, held)
+    s.reference = None
+    return s
+
+
+# (kind, slot) whose 1 + 2^-12 the checker CANNOT see on the stand-in's data, with the reason; asserted below, so that a bar that
+# is tightened later shows up here
+INVISIBLE = {}
+
+
+def test_every_other_checker_rejects_a_wrong_result(port_oracle):
+    """teeth, per kind of OTHER_KINDS and per compared array of each record: zeros and a factor 1 + 2^-12 are REJECTED"""
+    seen, passed = collections.Counter(), collections.defaultdict(list)
+    for what, r in _other_records(port_oracle, "48x96"):
+        check = M.CHECKERS[r.kind]
+        check(r, port_oracle)                                       # the unspoilt record passes
+        for slot in _slots(r):
+            a = getattr(r, slot[0])[slot[1]]
+            if not np.any(a):
+                continue                                            # (an all-zero gradient: nothing to spoil)
+            seen[r.kind, slot[0]] += 1
+            assert _rejected(check, _spoilt(r, slot, np.zeros_like), port_oracle), (what, slot, "zeros pass")
+            if not _rejected(check, _spoilt(r, slot, lambda v: (v * F32(1 + 2.0 ** -12)).astype(v.dtype)), port_oracle):
+                passed[r.kind, slot].append(what)
+    print("spoilt arrays per kind:", dict(seen))
+    print("a factor 1 + 2^-12 passes:", dict(passed))
+    assert set(passed) == set(INVISIBLE), (set(passed) ^ set(INVISIBLE), "scaled results that pass / bars that see them now")
+    assert {k for k, _ in seen} == set(OTHER_KINDS)
+    assert all(seen[k, "grad_in"] for k in OTHER_KINDS), "a kind without a gradient to spoil"
+
+
+# ---- LgaRegress: the LGA part, and the sign kink both ways -------------------------------------------------------------------------
+def _kink_site(oracle):
+    x, f, r, go = _lga_regress_site(*_ops(oracle), "train", oracle)
+    y64, E_y, und = M.lga_regress_undecided(x, f, r)
+    return x, f, r, go, y64, E_y, und
+
+
+def test_lga_regress_rejects_a_wrong_lga_pass(port_oracle):
+    """lga_ref64.MUTATIONS behind the regression: a dropped tap, zero padding -- in the whole op, and in each result alone"""
+    x, f, r, go, y64, E_y, und = _kink_site(port_oracle)
+    good = lrc.regress32(x, f, go, r)
+    M.check_lga_regress(lrc.record(x, f, r, good, go))
+    for what in lga_ref64.MUTATIONS:
+        y = lga_ref64.lga_forward(x, f, r, what).astype(F32)
+        bad = lrc.regress32(x, f, go, r, y)                          # the regression and its adjoint on the wrong pass ...
+        gy = M.m64.norm_regression_adjoint(y64, go)
+        bad["gx"], bad["gf"] = (g.astype(F32) for g in lga_ref64.lga_backward(x, f, gy, r, what))      # ... and the wrong adjoints of the right one
+        assert _rejected(M.check_lga_regress, lrc.record(x, f, r, bad, go)), what
+        for k in ("y", "out", "gx", "gf"):
+            assert _rejected(M.check_lga_regress, lrc.record(x, f, r, {**good, k: bad[k]}, go)), (what, k)
+
+
+def test_lga_regress_takes_the_calls_sign_where_float64_cannot_decide_and_nowhere_else(port_oracle):
+    """The experiment behind check_lga_regress's treatment of sgn(y), kept: on the stand-in's LgaRegress site an fp32 pass whose y
+    has the OTHER sign at the elements with |y64| <= chain_bound (no factor: -y64 is then within FACTOR x the bound of y64)
+    is accepted -- with sgn taken from float64 its gx stood at 16 .. 42 x the bar, the failure a device run showed now and
+    then.  The same flip at the decided elements nearest to the kink is rejected, by the name "sign"; and so is a backward
+    that used the wrong sign at ONE decided element while its y is right."""
+    x, f, r, go, y64, E_y, und = _kink_site(port_oracle)
+    y = lrc.forward32(x, f, r)
+    near = np.abs(y64) <= E_y / M.FACTOR
+    assert near.sum() >= 2 and und[near].all(), int(near.sum())
+    flipped = np.where(near, -y64, y).astype(F32)
+    q = M.check_lga_regress(lrc.record(x, f, r, lrc.regress32(x, f, go, r, flipped), go))
+    assert q["flipped"] == near.sum() and q["undecided"] == und.sum()
+    print(f"{int(near.sum())} of {int(und.sum())} undecided elements flipped: accepted,", " ".join(f"{k}={v:.3g}" for k, v in q.items()))
+    # decided elements, the nearest to the kink first
+    margin = np.where(und, np.inf, np.abs(y64) / np.maximum(E_y, 1e-300))
+    first = np.unravel_index(np.argsort(margin, axis=None)[:int(near.sum())], y64.shape)
+    decided = np.zeros(y64.shape, bool)
+    decided[first] = True
+    assert not und[decided].any() and margin[decided].min() > 1
+    wrong = np.where(decided, -y64, y).astype(F32)
+    with pytest.raises(AssertionError, match="sign"):
+        M.check_lga_regress(lrc.record(x, f, r, lrc.regress32(x, f, go, r, wrong), go))
+    # the right y kept, the wrong sign used at one decided element -- one with a gradient to show for it
+    good = lrc.regress32(x, f, go, r)
+    lever = np.where(und, 0.0, np.abs(go[:, None] * good["out"][:, None] / good["snorm"][:, None]) * np.ones(y64.shape))
+    one = np.zeros(y64.shape, bool)
+    one[np.unravel_index(np.argmax(lever), y64.shape)] = True
+    bad = lrc.regress32(x, f, go, r, np.where(one, -y, y))
+    with pytest.raises(AssertionError, match="gx"):
+        M.check_lga_regress(lrc.record(x, f, r, {**good, "gx": bad["gx"], "gf": bad["gf"]}, go))
+
+
 # ---- the stand-in and the rebinders -------------------------------------------------------------------------------------------
-_HELPERS = ("_fused_sga", "_fused_tail", "_fused_bn", "_fused_conv")
+_HELPERS =("_fused_sga", "_fused_tail", "_fused_bn", "_fused_conv")
 
 
 def _rebound(model):

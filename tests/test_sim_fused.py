@@ -2,6 +2,7 @@
 C ABI, against the reference's own torch statements executed on the CPU (oracle/fused_ref.py)."""
 import numpy as np
 
+import lga_regress_cases as lrc
 import parity_cases as pc
 import pytest
 import torch
@@ -283,6 +284,43 @@ def test_lga_pass_with_regression_epilogue(sim, port_oracle, shape, r, with_y):
     d = np.arange(D, dtype=np.float64)[None, :, None, None]
     np.testing.assert_allclose(snorm, np.abs(want.astype(np.float64)).sum(1), rtol=1e-5, atol=1e-5)
     np.testing.assert_allclose(sdy, (want.astype(np.float64) * d).sum(1), rtol=1e-5, atol=2e-4)
+
+
+def _lga_regress_on_the_emulator(sim):
+    """the three ABI entries LgaRegressFunction calls, in its order and with its fallback, on guarded buffers"""
+    from ganet_amd import _native
+
+    def call(x, f, go, r):
+        B, D, H, W = x.shape
+        keep = go is not None
+        y = np.full(x.shape, np.nan, np.float32)
+        snorm, sdy = (np.full((B, H, W), np.nan, np.float32) for _ in range(2))
+        try:
+            _call(sim, "ganet_lga_forward_regress", _p(x), _p(f), _p(y) if keep else None, _p(snorm), _p(sdy), B, D, H, W, r, None)
+            fused = True
+            snorm = np.maximum(snorm, np.float32(1e-12))
+            out = sdy / snorm
+            assert keep or np.isnan(y).all()
+        except _native.GanetError as e:
+            assert e.code == _native.E_UNSUPPORTED, e
+            fused, out = False, sdy
+            _call(sim, "ganet_lga_forward", _p(x), _p(f), _p(y), B, D, H, W, r, None)
+            _call(sim, "ganet_norm_disparity_regression_forward", _p(y), _p(out), _p(snorm), B, D, H, W, None)
+        if not keep:
+            return {"out": out, "fused": fused}
+        gy, gx, gf = np.full_like(x, np.nan), np.full_like(x, np.nan), np.full_like(f, np.nan)
+        _call(sim, "ganet_norm_disparity_regression_backward", _p(y), _p(out), _p(snorm), _p(go), _p(gy), B, D, H, W, None)
+        _call(sim, "ganet_lga_backward", _p(x), _p(f), _p(gy), _p(gx), _p(gf), B, D, H, W, r, 0, None)
+        return {"out": out, "y": y, "snorm": snorm, "gx": gx, "gf": gf, "fused": fused}
+
+    return call
+
+
+@pytest.mark.parametrize("case", lrc.CASES, ids=lrc.case_id)
+def test_lga_regress_against_float64(sim, case):
+    """tests/lga_regress_cases.py: the fused pass, its fallback and the backward chain against float64 through
+    model_calls.check_lga_regress -- general values, y planted at the sign kink, a clamped norm; with and without the volume"""
+    lrc.run(case, _lga_regress_on_the_emulator(sim))
 
 
 def _bn3d(C, seed, affine=True):
