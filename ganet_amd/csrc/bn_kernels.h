@@ -49,26 +49,6 @@ struct BnGeom {
   int Rs, Rn;   // blocks along a slice x blocks over the slices of one channel; R = Rs * Rn rows of 2 doubles per channel
 };
 
-template <int V> GA_DEV void bn_load(const float *p, float (&o)[V])
-{
-  if constexpr (V == 4) {
-    const f4 a = *reinterpret_cast<const f4 *>(p);
-    o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w;
-  } else {
-    o[0] = *p;
-  }
-}
-
-template <int V> GA_DEV void bn_store(float *p, const float (&o)[V])
-{
-  if constexpr (V == 4) {
-    f4 a; a.x = o[0]; a.y = o[1]; a.z = o[2]; a.w = o[3];
-    *reinterpret_cast<f4 *>(p) = a;
-  } else {
-    *p = o[0];
-  }
-}
-
 // the pre-activation, the one expression forward and backward share
 GA_DEV float bn_z(float x, float scale, float shift, float rem, bool has_rem)
 {
@@ -139,7 +119,7 @@ bn_stat_partials(const float *__restrict__ x, double *__restrict__ ws, BnGeom g)
     const float *xs = x + ((i64)n * g.C + c) * g.S;
     for (i64 i = (i64)rs * BN_BLOCK + threadIdx.x; i < SV; i += stride) {
       float a[V];
-      bn_load<V>(xs + i * V, a);
+      st_load<st_f32, V>(xs + i * V, a);
 #pragma unroll
       for (int j = 0; j < V; j++) {
         const double d = (double)a[j] - x0;
@@ -163,14 +143,14 @@ GA_DEV void bn_apply_share(const float *x, const float *__restrict__ rem, float 
     const i64 base = ((i64)n * g.C + c) * g.S;
     for (i64 i = (i64)rs * BN_BLOCK + threadIdx.x; i < SV; i += stride) {
       float a[V], r[V], o[V];
-      bn_load<V>(x + base + i * V, a);
-      if (has_rem) bn_load<V>(rem + base + i * V, r);
+      st_load<st_f32, V>(x + base + i * V, a);
+      if (has_rem) st_load<st_f32, V>(rem + base + i * V, r);
 #pragma unroll
       for (int j = 0; j < V; j++) {
         const float z = bn_z(a[j], scale, shift, has_rem ? r[j] : 0.f, has_rem);
         o[j] = relu ? relu_keep_nan(z) : z;
       }
-      bn_store<V>(y + base + i * V, o);
+      st_store<st_f32, V>(y + base + i * V, o);
     }
   }
 }
@@ -234,9 +214,9 @@ bn_bwd_partials(const float *__restrict__ x, const float *__restrict__ rem, cons
     const i64 base = ((i64)n * g.C + c) * g.S;
     for (i64 i = (i64)rs * BN_BLOCK + threadIdx.x; i < SV; i += stride) {
       float a[V], r[V], d[V];
-      bn_load<V>(x + base + i * V, a);
-      bn_load<V>(gy + base + i * V, d);
-      if (relu && has_rem) bn_load<V>(rem + base + i * V, r);
+      st_load<st_f32, V>(x + base + i * V, a);
+      st_load<st_f32, V>(gy + base + i * V, d);
+      if (relu && has_rem) st_load<st_f32, V>(rem + base + i * V, r);
 #pragma unroll
       for (int j = 0; j < V; j++) {
         float gj = d[j];
@@ -280,16 +260,16 @@ bn_bwd_apply(const float *__restrict__ x, const float *__restrict__ rem, const f
     const i64 base = ((i64)n * g.C + c) * g.S;
     for (i64 i = (i64)rs * BN_BLOCK + threadIdx.x; i < SV; i += stride) {
       float a[V], r[V], d[V], o[V];
-      bn_load<V>(x + base + i * V, a);
-      bn_load<V>(gy + base + i * V, d);
-      if (relu && has_rem) bn_load<V>(rem + base + i * V, r);
+      st_load<st_f32, V>(x + base + i * V, a);
+      st_load<st_f32, V>(gy + base + i * V, d);
+      if (relu && has_rem) st_load<st_f32, V>(rem + base + i * V, r);
 #pragma unroll
       for (int j = 0; j < V; j++) {
         if (relu) d[j] = bn_z(a[j], scale, shift, has_rem ? r[j] : 0.f, has_rem) <= 0.f ? 0.f : d[j];
         o[j] = scale * (d[j] - k1 - (a[j] - mean) * q);
       }
-      if (gx) bn_store<V>(gx + base + i * V, o);
-      if (grem) bn_store<V>(grem + base + i * V, d);
+      if (gx) st_store<st_f32, V>(gx + base + i * V, o);
+      if (grem) st_store<st_f32, V>(grem + base + i * V, d);
     }
   }
 }

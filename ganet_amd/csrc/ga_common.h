@@ -495,6 +495,7 @@ GA_DEV uint32_t f32x2_to_bf16(float lo, float hi)
 struct st_f32 {
   typedef float T;
   static constexpr int CODE = 0;
+  static GA_DEV float get(float v) { return v; }
 };
 struct st_f16 {
   typedef uint16_t T;
@@ -520,13 +521,18 @@ struct st_raw16 {
   static GA_DEV uint32_t pack2(float lo, float hi) { return ((uint32_t)f2i(lo) & 0xffffu) | ((uint32_t)f2i(hi) << 16); }
 };
 
-// V = 8: 16-byte requests -- one for eight 16-bit elements, two for eight floats; V = 1: the scalar twin
+// The lane-vector load / store of every streaming kernel.  V = 8: 16-byte requests -- one for eight 16-bit elements, two for
+// eight floats; V = 4 (4-byte storage only): one; V = 1: the scalar twin
 template <typename ST, int V> GA_DEV void st_load(const typename ST::T *p, float (&o)[V])
 {
+  static_assert(V == 1 || V == 8 || (V == 4 && sizeof(typename ST::T) == 4), "st_load: no such lane vector");
   if constexpr (sizeof(typename ST::T) == 4) {
     if constexpr (V == 8) {
       const f4 a = *reinterpret_cast<const f4 *>(p), b = *reinterpret_cast<const f4 *>(p + 4);
       o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
+    } else if constexpr (V == 4) {
+      const f4 a = *reinterpret_cast<const f4 *>(p);
+      o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w;
     } else {
       o[0] = *p;
     }
@@ -547,12 +553,16 @@ template <typename ST, int V> GA_DEV void st_load(const typename ST::T *p, float
 
 template <typename ST, int V> GA_DEV void st_store(typename ST::T *p, const float (&o)[V])
 {
+  static_assert(V == 1 || V == 8 || (V == 4 && sizeof(typename ST::T) == 4), "st_store: no such lane vector");
   if constexpr (sizeof(typename ST::T) == 4) {
     if constexpr (V == 8) {
       f4 a, b;
       a.x = o[0]; a.y = o[1]; a.z = o[2]; a.w = o[3]; b.x = o[4]; b.y = o[5]; b.z = o[6]; b.w = o[7];
       *reinterpret_cast<f4 *>(p) = a;
       *reinterpret_cast<f4 *>(p + 4) = b;
+    } else if constexpr (V == 4) {
+      f4 a; a.x = o[0]; a.y = o[1]; a.z = o[2]; a.w = o[3];
+      *reinterpret_cast<f4 *>(p) = a;
     } else {
       *p = o[0];
     }
@@ -565,6 +575,16 @@ template <typename ST, int V> GA_DEV void st_store(typename ST::T *p, const floa
       *p = ST::put(o[0]);
     }
   }
+}
+
+// planes d0 ... d0 + U - 1 of the lane's column `col` (plane stride HW), V pixels each, UNCONDITIONALLY: the plane index is
+// clamped to Dn - 1 and the caller masks what it does with planes past the end.  A load under a condition is followed by
+// s_waitcnt vmcnt(0), one memory round trip per plane; this way U requests are in flight -- and no address leaves the column
+// (the emulator tests put every caller's buffers behind guard pages to hold it to that).
+template <int U, int V> GA_DEV void load_planes(const float *col, int d0, int Dn, i64 HW, float (&v)[U][V])
+{
+#pragma unroll
+  for (int u = 0; u < U; u++) st_load<st_f32, V>(col + (i64)(d0 + u < Dn ? d0 + u : Dn - 1) * HW, v[u]);
 }
 
 // MI355X: workgroup b runs on XCD b % 8 (observed, speed only).  Give each XCD a

@@ -259,8 +259,10 @@ int launch_scan_bwdg_f32mask(const float *g, const float *mask, const uint16_t *
   ScanGeom geo = make_geom(S, D, H, W, dir, true);
   const int block = 64, lpb = block / GD;
   const int grid = (geo.total_lines + lpb - 1) / lpb;
-  GA_LAUNCH((sga_bwdg_strided<GD, DPL, bwd_sb(DPL), float>), dim3(grid), dim3(block), st, g, mask, kp,
-            gout, G, geo, dir);
+  // (scan_bwdg_f32mask asks pick_pair for 16 lanes and gets 64 only past the last 16-lane pair: no 64-lane pair that small)
+  if constexpr (GD == 16 || GD * DPL > 16 * 17)
+    GA_LAUNCH((sga_bwdg_strided<GD, DPL, bwd_sb(DPL), float>), dim3(grid), dim3(block), st, g, mask, kp,
+              gout, G, geo, dir);
   return check_launch("sga adjoint scan (f32 mask)");
 }
 
@@ -287,8 +289,8 @@ int row_fwd(const float *x, const float *g, float *A, int S, int D, int H, int W
 }
 
 // ---- vertical scans over LDS-staged 16-column blocks (sga_col_kernels.h) ----------------------------
-size_t col_smem_fwd(int D) { return sizeof(float) * ((size_t)2 * COL_NC * D * COL_SBV + COL_NC * 5 * COL_SBV); }
-size_t col_smem_bwdg(int D)
+constexpr size_t col_smem_fwd(int D) { return sizeof(float) * ((size_t)2 * COL_NC * D * COL_SBV + COL_NC * 5 * COL_SBV); }
+constexpr size_t col_smem_bwdg(int D)
 {
   return sizeof(float) * ((size_t)2 * COL_NC * D * COL_SBV + COL_NC * 5 * COL_SBV + COL_NC * COL_SBV) +
          (size_t)D * COL_SBV * 16;
@@ -297,6 +299,10 @@ bool colblock_ok(int D, int W, int dir, size_t smem)
 {
   return opts().colblock && dir < 2 && W % 4 == 0 && D <= 16 * 13 && smem <= ROW_SMEM_MAX;
 }
+// disparities per lane the column blocks are compiled for: what the LDS cap lets through (forward D <= 125, adjoint less),
+// and every caller of col_fwd / col_bwdg has asked colblock_ok
+constexpr bool col_dpl_fits(int dpl) { return dpl <= 9; }
+static_assert(col_smem_fwd(16 * 9 + 1) > ROW_SMEM_MAX && col_smem_bwdg(16 * 9 + 1) > ROW_SMEM_MAX, "col_dpl_fits: D = 145 fits now");
 
 ColGeom col_geom(int D, int H, int W, int out_mode, int tiled)
 {
@@ -315,7 +321,8 @@ int col_fwd(const float *x, const float *g, float *A, int S, int D, int H, int W
   const dim3 grid((W + COL_NC - 1) / COL_NC, S), block(256);
   with_row_dpl(dpl, [&](auto P) {
     with_flags([&](auto asc, auto fl) {
-      GA_LAUNCH_SMEM((sga_col_fwd<decltype(P)::value, decltype(asc)::value, decltype(fl)::value>), grid, block, smem, st, x, g, A, geo);
+      if constexpr (col_dpl_fits(decltype(P)::value) && (decltype(fl)::value || decltype(P)::value > 1))      // (one disparity per lane is always full)
+        GA_LAUNCH_SMEM((sga_col_fwd<decltype(P)::value, decltype(asc)::value, decltype(fl)::value>), grid, block, smem, st, x, g, A, geo);
     }, dir == 0, full);
   });
   return check_launch("sga column-block forward");
@@ -387,7 +394,8 @@ int col_bwdg(const float *g, const uint8_t *mask, const uint16_t *kp, const floa
   with_row_dpl(dpl, [&](auto P) {
     with_flags([&](auto asc, auto m, auto fl) {
       constexpr bool FL = decltype(fl)::value && (decltype(P)::value == 3 || decltype(P)::value == 5);
-      GA_LAUNCH_SMEM((sga_col_bwdg<decltype(P)::value, decltype(asc)::value, decltype(m)::value, FL>), grid, block, smem, st, g, mask, kp, gout, G, geo, dir);
+      if constexpr (col_dpl_fits(decltype(P)::value))
+        GA_LAUNCH_SMEM((sga_col_bwdg<decltype(P)::value, decltype(asc)::value, decltype(m)::value, FL>), grid, block, smem, st, g, mask, kp, gout, G, geo, dir);
     }, dir == 1, m16, full);
   });
   return check_launch("sga column-block adjoint scan");
@@ -520,11 +528,11 @@ int bwd_point(const float *x, float *gx, const PointArgs &pa, int ndir, int N, i
   const i64 npix = (i64)N * C * H * W;
   const int pb = 256;      // (64 / 128 measured equal)
   const dim3 grid(clamp_grid(npix, pb, (i64)256 * 32 * (256 / pb)));
-  // (the tiled layout of G_down / G_up is compiled for the four-direction, non-accumulating form alone: sga_bwd_point<4, false, true>)
+  // (every four-direction caller overwrites grad_x; the tiled layout of G_down / G_up exists for that form alone: sga_bwd_point<4, false, true>)
   with_flags([&](auto four, auto acc, auto til) {
     constexpr int ND = decltype(four)::value ? 4 : 1;
     constexpr bool ACC = decltype(acc)::value, TG = decltype(til)::value;
-    if constexpr (!TG || (ND == 4 && !ACC))
+    if constexpr (ND == 4 ? !ACC : !TG)
       GA_LAUNCH((sga_bwd_point<ND, ACC, TG>), grid, dim3(pb), st, x, gx, pa, D, H, W, npix);
   }, ndir == 4, accumulate != 0, ndir == 4 && !accumulate && tiled);
   return check_launch("sga per-pixel gradients");
@@ -974,10 +982,10 @@ GA_EXPORT int ganet_sga_forward_infer(const float *x, const float *g0, const flo
   if (!A_ws) return fail(GANET_E_INVALID, "%s: this shape needs the A_ws scratch (see ganet_sga_forward_infer_scratch)", who);
   for (int d = 0; d < 4; d++) GA_TRY(scan_fwd(x, gs[d], A_ws + d * n, N, C, D, H, W, d, st));
   const bool vec = slice % 4 == 0 && aligned16(A_ws, out);
-  with_flags([&](auto v) {
+  with_width<4>(vec, [&](auto v) {
     GA_LAUNCH((sga_merge_infer<decltype(v)::value>), dim3(ew_grid(vec ? n / 4 : n)), dim3(256), st, A_ws, A_ws + n, A_ws + 2 * n,
               A_ws + 3 * n, out, bn_scale, bn_shift, C, slice, n);
-  }, vec);
+  });
   return check_launch("sga merge (inference)");
 }
 
@@ -1212,7 +1220,7 @@ GA_EXPORT int ganet_cost_volume_forward(const float *x, const float *y, float *c
   if (W % 4 == 0 && aligned16(x, cost))
     GA_LAUNCH(cost_volume_fwd4, dim3(ew_grid(n / 4)), dim3(256), (hipStream_t)stream, x, y, cost, N, C, Dn, H, W);
   else
-    GA_LAUNCH(cost_volume_fwd, dim3(ew_grid(n)), dim3(256), (hipStream_t)stream, x, y, cost, N, C, Dn, H, W);
+    GA_LAUNCH(cost_volume_fwd<float>, dim3(ew_grid(n)), dim3(256), (hipStream_t)stream, x, y, cost, N, C, Dn, H, W);
   return check_launch("cost volume forward");
 }
 
@@ -1372,10 +1380,10 @@ GA_EXPORT int ganet_softmin_forward(const float *x, float *y, int N, int Dn, int
   GA_TRY(check_ptrs(who, x, y));
   GA_TRY(check_positive(who, N, Dn, H, W));
   const i64 HW = (i64)H * W;
-  if (HW % 4 == 0 && aligned16(x, y))
-    GA_LAUNCH(softmin_fwd4, dim3(ew_grid((i64)N * HW / 4)), dim3(256), (hipStream_t)stream, x, y, N, Dn, HW);
-  else
-    GA_LAUNCH(softmin_fwd, dim3(ew_grid((i64)N * HW)), dim3(256), (hipStream_t)stream, x, y, N, Dn, HW);
+  with_width<4>(HW % 4 == 0 && aligned16(x, y), [&](auto v) {
+    constexpr int V = decltype(v)::value;
+    GA_LAUNCH(softmin_fwd<V>, dim3(ew_grid((i64)N * HW / V)), dim3(256), (hipStream_t)stream, x, y, N, Dn, HW);
+  });
   return check_launch("softmin forward");
 }
 
@@ -1780,7 +1788,9 @@ void launch_cast(const void *src, void *dst, i64 n, hipStream_t st)
   const bool vec = aligned16(src, dst) && n >= MX_V;
   with_width<MX_V>(vec, [&](auto v) {
     constexpr int V = decltype(v)::value;
-    GA_LAUNCH((cast_kernel<Ts, Td, V>), dim3(ew_grid(n / V)), dim3(256), st, sp, dp, n);
+    // (16 bits to the same 16 bits is ganet_cast's raw copy, never a typed kernel)
+    if constexpr (!(std::is_same_v<Ts, Td> && Ts::CODE > 0))
+      GA_LAUNCH((cast_kernel<Ts, Td, V>), dim3(ew_grid(n / V)), dim3(256), st, sp, dp, n);
   });
 }
 }  // namespace
@@ -1852,7 +1862,7 @@ GA_EXPORT int ganet_cost_volume_forward_16(const void *x, const void *y, void *c
   if (W % MX_V == 0 && aligned16(x, cost))
     GA_LAUNCH(cost_volume_fwd16, dim3(ew_grid(n / MX_V)), dim3(256), (hipStream_t)stream, xp, yp, cp, N, C, Dn, H, W);
   else
-    GA_LAUNCH(cost_volume_fwd16s, dim3(ew_grid(n)), dim3(256), (hipStream_t)stream, xp, yp, cp, N, C, Dn, H, W);
+    GA_LAUNCH(cost_volume_fwd<uint16_t>, dim3(ew_grid(n)), dim3(256), (hipStream_t)stream, xp, yp, cp, N, C, Dn, H, W);
   return check_launch("cost volume forward (16-bit)");
 }
 
@@ -1876,7 +1886,7 @@ GA_EXPORT int ganet_l1_normalize_forward_mixed(const void *x, float *y0, float *
   const uint16_t *xp = (const uint16_t *)x;
   with_st16(x_type, [&](auto t16) {
     with_int_else<0, 5, 75>(K, [&](auto KC) {
-      GA_LAUNCH((l1norm_fwd_mixed<decltype(KC)::value, typename decltype(t16)::type>), grid, block, st, xp, p, N, G, C, K, HW);
+      GA_LAUNCH((l1norm_fwd<decltype(KC)::value, typename decltype(t16)::type>), grid, block, st, xp, p, N, G, C, K, HW);
     });
   });
   return check_launch("l1 normalise forward (mixed)");

@@ -64,16 +64,6 @@ GA_DEV float loss_slope(float v, int kind, float knee, float span, float far)
   return v;
 }
 
-template <int V> GA_DEV void loss_load(const float *p, float (&o)[V])
-{
-  if constexpr (V == 4) {
-    const f4 a = *reinterpret_cast<const f4 *>(p);
-    o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w;
-  } else {
-    o[0] = *p;
-  }
-}
-
 // Launch 1: V (1 or 4: 16-byte loads) pixels per lane and trip, fp64 accumulators per thread, a fixed-order tree through
 // LDS, one row of 1 + 3P partial sums per block.
 template <int V>
@@ -91,7 +81,7 @@ loss_partials(LossMaps m, const float *__restrict__ target, const float *__restr
   for (i64 q = (i64)blockIdx.x * blockDim.x + threadIdx.x; q < total / V; q += stride) {
     float t[V], p[V];
     bool ok[V];
-    loss_load<V>(target + q * V, t);
+    st_load<st_f32, V>(target + q * V, t);
 #pragma unroll
     for (int j = 0; j < V; j++) {
       ok[j] = loss_valid(t[j], hi, lo, mask_mode);
@@ -100,7 +90,7 @@ loss_partials(LossMaps m, const float *__restrict__ target, const float *__restr
 #pragma unroll
     for (int k = 0; k < 3; k++) {
       if (k < P) {
-        loss_load<V>(m.p[k] + q * V, p);
+        st_load<st_f32, V>(m.p[k] + q * V, p);
 #pragma unroll
         for (int j = 0; j < V; j++) {
           const float v = fabsf(p[j] - t[j]);
@@ -172,13 +162,13 @@ loss_bwd(LossMaps m, const float *__restrict__ target, const float *__restrict__
   for (i64 q = (i64)blockIdx.x * blockDim.x + threadIdx.x; q < total / V; q += stride) {
     float t[V], p[V], g[V];
     bool ok[V];
-    loss_load<V>(target + q * V, t);
+    st_load<st_f32, V>(target + q * V, t);
 #pragma unroll
     for (int j = 0; j < V; j++) ok[j] = count > 0.0 && loss_valid(t[j], hi, lo, mask_mode);
 #pragma unroll
     for (int k = 0; k < 3; k++) {
       if (k < P && m.g[k]) {
-        loss_load<V>(m.p[k] + q * V, p);
+        st_load<st_f32, V>(m.p[k] + q * V, p);
 #pragma unroll
         for (int j = 0; j < V; j++) {
           const float r = p[j] - t[j];
@@ -186,12 +176,7 @@ loss_bwd(LossMaps m, const float *__restrict__ target, const float *__restrict__
           const float gv = sg * loss_slope(fabsf(r), m.kind[k], knee, span, far) * c[k];
           g[j] = ok[j] ? gv : 0.f;
         }
-        if constexpr (V == 4) {
-          f4 o; o.x = g[0]; o.y = g[1]; o.z = g[2]; o.w = g[3];
-          *reinterpret_cast<f4 *>(m.g[k] + q * V) = o;
-        } else {
-          m.g[k][q] = g[0];
-        }
+        st_store<st_f32, V>(m.g[k] + q * V, g);
       }
     }
   }

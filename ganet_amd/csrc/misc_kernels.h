@@ -7,10 +7,11 @@
 
 namespace ga {
 
-// cost[n,c,i,h,w] = x[n,c,h,w] (c<C) | y[n,c-C,h,w-i] (c>=C) for w>=i, else 0
+// cost[n,c,i,h,w] = x[n,c,h,w] (c<C) | y[n,c-C,h,w-i] (c>=C) for w>=i, else 0.  A copy with zeros: T = float, or uint16_t for
+// either 16-bit format (0x0000 is zero in both)
+template <typename T>
 __global__ void __launch_bounds__(256)
-cost_volume_fwd(const float *__restrict__ x, const float *__restrict__ y, float *__restrict__ cost,
-                int N, int C, int Dn, int H, int W)
+cost_volume_fwd(const T *__restrict__ x, const T *__restrict__ y, T *__restrict__ cost, int N, int C, int Dn, int H, int W)
 {
   const i64 total = (i64)N * 2 * C * Dn * H * W;
   const i64 stride = (i64)gridDim.x * blockDim.x;
@@ -21,7 +22,7 @@ cost_volume_fwd(const float *__restrict__ x, const float *__restrict__ y, float 
     const int i = (int)(r % Dn); r /= Dn;
     const int c = (int)(r % (2 * C));
     const int n = (int)(r / (2 * C));
-    float v = 0.f;
+    T v = 0;
     if (w >= i) {
       if (c < C) v = x[(((i64)n * C + c) * H + h) * W + w];
       else v = y[(((i64)n * C + (c - C)) * H + h) * W + (w - i)];
@@ -32,7 +33,8 @@ cost_volume_fwd(const float *__restrict__ x, const float *__restrict__ y, float 
 
 // the same with four consecutive columns per lane (W % 4 == 0, 16-byte aligned buffers): one index decomposition per
 // 16-byte store instead of per element (0.23 -> 0.06 ms at [1,64,65,80,208]); the shifted right-image samples are four
-// scalar loads (they hit L1/L2: the 2*C source planes are read Dn times)
+// scalar loads (they hit L1/L2: the 2*C source planes are read Dn times).
+// Not one template with cost_volume_fwd16 (mixed_kernels.h): the shifted right-image loads differ with the element width.
 static __global__ void __launch_bounds__(256)
 cost_volume_fwd4(const float *__restrict__ x, const float *__restrict__ y, float *__restrict__ cost,
                  int N, int C, int Dn, int H, int W)
@@ -47,24 +49,22 @@ cost_volume_fwd4(const float *__restrict__ x, const float *__restrict__ y, float
     const int i = (int)(r % Dn); r /= Dn;
     const int c = (int)(r % (2 * C));
     const int n = (int)(r / (2 * C));
-    f4 v;
+    float v[4];
     if (c < C) {
-      v = *reinterpret_cast<const f4 *>(x + (((i64)n * C + c) * H + h) * W + w);
-      if (w < i) v.x = 0.f;
-      if (w + 1 < i) v.y = 0.f;
-      if (w + 2 < i) v.z = 0.f;
-      if (w + 3 < i) v.w = 0.f;
+      st_load<st_f32, 4>(x + (((i64)n * C + c) * H + h) * W + w, v);
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+        if (w + j < i) v[j] = 0.f;
     } else {
       const float *yr = y + (((i64)n * C + (c - C)) * H + h) * W;
       const int s0 = w - i;                        // source column of the first element (may be negative)
-      const float a0 = yr[s0 > 0 ? s0 : 0], a1 = yr[s0 + 1 > 0 ? s0 + 1 : 0];
-      const float a2 = yr[s0 + 2 > 0 ? s0 + 2 : 0], a3 = yr[s0 + 3 > 0 ? s0 + 3 : 0];
-      v.x = s0 >= 0 ? a0 : 0.f;
-      v.y = s0 + 1 >= 0 ? a1 : 0.f;
-      v.z = s0 + 2 >= 0 ? a2 : 0.f;
-      v.w = s0 + 3 >= 0 ? a3 : 0.f;
+      float a[4];
+#pragma unroll
+      for (int j = 0; j < 4; j++) a[j] = yr[s0 + j > 0 ? s0 + j : 0];
+#pragma unroll
+      for (int j = 0; j < 4; j++) v[j] = s0 + j >= 0 ? a[j] : 0.f;
     }
-    *reinterpret_cast<f4 *>(cost + (q << 2)) = v;
+    st_store<st_f32, 4>(cost + (q << 2), v);
   }
 }
 
@@ -119,12 +119,11 @@ disp_regression_fwd(const float *__restrict__ x, float *__restrict__ out, int N,
     const float *xp = x + n * Dn * HW + pix;
     float acc = 0.f;
     for (int d0 = 0; d0 < Dn; d0 += 8) {       // 8 loads in flight per lane (same summation order)
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; u++) v[u] = xp[(i64)(d0 + u < Dn ? d0 + u : Dn - 1) * HW];
+      float v[8][1];
+      load_planes(xp, d0, Dn, HW, v);
 #pragma unroll
       for (int u = 0; u < 8; u++)
-        if (d0 + u < Dn) acc = fmaf(v[u], (float)(d0 + u), acc);
+        if (d0 + u < Dn) acc = fmaf(v[u][0], (float)(d0 + u), acc);
     }
     out[o] = acc;
   }
@@ -146,7 +145,8 @@ disp_regression_bwd(const float *__restrict__ gout, float *__restrict__ gx, int 
 }
 
 // the same with four pixels per lane marching over d (HW % 4 == 0, 16-byte aligned buffers): gout is read once,
-// every store is 16 bytes and no index is divided per element (0.10 -> 0.03 ms at [1,193,240,624])
+// every store is 16 bytes and no index is divided per element (0.10 -> 0.03 ms at [1,193,240,624]).
+// Not one template with disp_regression_bwd: that is one lane per ELEMENT, this a march down a column.
 static __global__ void __launch_bounds__(256)
 disp_regression_bwd4(const float *__restrict__ gout, float *__restrict__ gx, int N, int Dn, i64 HW)
 {
@@ -154,13 +154,14 @@ disp_regression_bwd4(const float *__restrict__ gout, float *__restrict__ gx, int
   const i64 stride = (i64)gridDim.x * blockDim.x;
   for (i64 q = (i64)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += stride) {
     const i64 n = q / (HW >> 2), pix = (q - n * (HW >> 2)) << 2;
-    const f4 g = *reinterpret_cast<const f4 *>(gout + n * HW + pix);
+    float g[4], r[4];
+    st_load<st_f32, 4>(gout + n * HW + pix, g);
     float *gp = gx + n * Dn * HW + pix;
     for (int d = 0; d < Dn; d++) {
       const float df = (float)d;
-      f4 r;
-      r.x = g.x * df; r.y = g.y * df; r.z = g.z * df; r.w = g.w * df;
-      *reinterpret_cast<f4 *>(gp + (i64)d * HW) = r;
+#pragma unroll
+      for (int j = 0; j < 4; j++) r[j] = g[j] * df;
+      st_store<st_f32, 4>(gp + (i64)d * HW, r);
     }
   }
 }
@@ -182,10 +183,11 @@ struct NormPtrs {
 
 // x [N][G][C][K][HW] -> y_g [N][C][K][HW], g < G <= 4: L1-normalise over K (the SGABlock split: G = 4,
 // K = 5; LGA filters: G = C = 1, K = 3(2r+1)^2).  One lane per (n,g,c,pixel); the K values of a lane
-// stay in registers when K is a template constant, otherwise the lane walks its column twice.
-template <int KT>
+// stay in registers when K is a template constant, otherwise the lane walks its column twice.  Tx: the storage of x (fp32, or
+// 16-bit in front of an fp32 op: the up-cast is exact, sum and clamp are this one expression); the outputs are fp32.
+template <int KT, typename Tx = st_f32>
 __global__ void __launch_bounds__(256)
-l1norm_fwd(const float *__restrict__ x, NormPtrs p, int N, int G, int C, int Krt, i64 HW)
+l1norm_fwd(const typename Tx::T *__restrict__ x, NormPtrs p, int N, int G, int C, int Krt, i64 HW)
 {
   const int K = KT > 0 ? KT : Krt;
   const i64 total = (i64)N * G * C * HW;
@@ -195,22 +197,22 @@ l1norm_fwd(const float *__restrict__ x, NormPtrs p, int N, int G, int C, int Krt
     const int c = (int)(o % C);
     const int g = (int)((o / C) % G);
     const i64 n = o / ((i64)C * G);
-    const float *xin = x + o * K * HW + pix;
+    const typename Tx::T *xin = x + o * K * HW + pix;
     float *yb = g == 0 ? p.y[0] : g == 1 ? p.y[1] : g == 2 ? p.y[2] : p.y[3];
     float *yo = yb + (n * C + c) * K * HW + pix;
     if (KT > 0) {
       float v[KT > 0 ? KT : 1];
       float sa = 0.f;
 #pragma unroll
-      for (int t = 0; t < KT; t++) { v[t] = xin[(i64)t * HW]; sa += fabsf(v[t]); }
+      for (int t = 0; t < KT; t++) { v[t] = Tx::get(xin[(i64)t * HW]); sa += fabsf(v[t]); }
       const float sden = fmaxf(sa, GA_NORM_EPS);
 #pragma unroll
       for (int t = 0; t < KT; t++) yo[(i64)t * HW] = v[t] / sden;
     } else {
       float sa = 0.f;
-      for (int t = 0; t < K; t++) sa += fabsf(xin[(i64)t * HW]);
+      for (int t = 0; t < K; t++) sa += fabsf(Tx::get(xin[(i64)t * HW]));
       const float sden = fmaxf(sa, GA_NORM_EPS);
-      for (int t = 0; t < K; t++) yo[(i64)t * HW] = xin[(i64)t * HW] / sden;
+      for (int t = 0; t < K; t++) yo[(i64)t * HW] = Tx::get(xin[(i64)t * HW]) / sden;
     }
   }
 }
@@ -277,12 +279,11 @@ norm_disp_regression_fwd(const float *__restrict__ x, float *__restrict__ out, f
     const float *xp = x + n * Dn * HW + pix;
     float acc = 0.f, sa = 0.f;
     for (int d0 = 0; d0 < Dn; d0 += 8) {       // 8 loads in flight per lane
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; u++) v[u] = xp[(i64)(d0 + u < Dn ? d0 + u : Dn - 1) * HW];
+      float v[8][1];
+      load_planes(xp, d0, Dn, HW, v);
 #pragma unroll
       for (int u = 0; u < 8; u++)
-        if (d0 + u < Dn) { acc = fmaf(v[u], (float)(d0 + u), acc); sa += fabsf(v[u]); }
+        if (d0 + u < Dn) { acc = fmaf(v[u][0], (float)(d0 + u), acc); sa += fabsf(v[u][0]); }
     }
     const float sden = fmaxf(sa, GA_NORM_EPS);
     out[o] = acc / sden;
@@ -311,7 +312,8 @@ norm_disp_regression_bwd(const float *__restrict__ x, const float *__restrict__ 
   }
 }
 
-// the same, four pixels per lane marching over d (HW % 4 == 0, 16-byte aligned buffers), 4 planes in flight
+// the same, four pixels per lane marching over d (HW % 4 == 0, 16-byte aligned buffers), 4 planes in flight.
+// Not one template with norm_disp_regression_bwd: that rounds gout * ((d - o sgn) / s), this (gout / s) * (d - o sgn).
 static __global__ void __launch_bounds__(256)
 norm_disp_regression_bwd4(const float *__restrict__ x, const float *__restrict__ out,
                           const float *__restrict__ snorm, const float *__restrict__ gout,
@@ -321,78 +323,90 @@ norm_disp_regression_bwd4(const float *__restrict__ x, const float *__restrict__
   const i64 stride = (i64)gridDim.x * blockDim.x;
   for (i64 q = (i64)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += stride) {
     const i64 n = q / (HW >> 2), pix = (q - n * (HW >> 2)) << 2;
-    const f4 so = *reinterpret_cast<const f4 *>(snorm + n * HW + pix);
-    const f4 oo = *reinterpret_cast<const f4 *>(out + n * HW + pix);
-    const f4 go = *reinterpret_cast<const f4 *>(gout + n * HW + pix);
-    const float sd[4] = {so.x, so.y, so.z, so.w}, gg[4] = {go.x, go.y, go.z, go.w};
-    float ov[4] = {oo.x, oo.y, oo.z, oo.w};
+    float sd[4], ov[4], gg[4];
+    st_load<st_f32, 4>(snorm + n * HW + pix, sd);
+    st_load<st_f32, 4>(out + n * HW + pix, ov);
+    st_load<st_f32, 4>(gout + n * HW + pix, gg);
     float gs[4];                                  // gout / s: one division per pixel, not per element
 #pragma unroll
     for (int j = 0; j < 4; j++) { ov[j] = sd[j] > GA_NORM_EPS ? ov[j] : 0.f; gs[j] = gg[j] / sd[j]; }
     const float *xp = x + n * Dn * HW + pix;
     float *gp = gx + n * Dn * HW + pix;
     for (int d0 = 0; d0 < Dn; d0 += 4) {
-      f4 v[4];
-#pragma unroll
-      for (int u = 0; u < 4; u++) v[u] = *reinterpret_cast<const f4 *>(xp + (i64)(d0 + u < Dn ? d0 + u : Dn - 1) * HW);
+      float v[4][4];
+      load_planes(xp, d0, Dn, HW, v);
 #pragma unroll
       for (int u = 0; u < 4; u++) {
         if (d0 + u < Dn) {
           const float df = (float)(d0 + u);
-          const float xv[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
           float r[4];
 #pragma unroll
           for (int j = 0; j < 4; j++) {
-            const float sg = xv[j] > 0.f ? 1.f : (xv[j] < 0.f ? -1.f : 0.f);
+            const float sg = v[u][j] > 0.f ? 1.f : (v[u][j] < 0.f ? -1.f : 0.f);
             r[j] = gs[j] * (df - ov[j] * sg);
           }
-          f4 o_; o_.x = r[0]; o_.y = r[1]; o_.z = r[2]; o_.w = r[3];
-          *reinterpret_cast<f4 *>(gp + (i64)(d0 + u) * HW) = o_;
+          st_store<st_f32, 4>(gp + (i64)(d0 + u) * HW, r);
         }
       }
     }
   }
 }
 
-// y[n,d,h,w] = softmax_d(-x)  (nn.Softmin(dim=1), models/GANet_deep.py:244): one lane per pixel, two walks over its
-// column (running max + rescaled sum, then the normalised exponentials), 8 loads in flight.  Stock PyTorch runs a
-// negation kernel plus a strided softmax (0.24 ms at [1,193,240,624]).
-static __global__ void __launch_bounds__(256)
+// y[n,d,h,w] = softmax_d(-x)  (nn.Softmin(dim=1), models/GANet_deep.py:244): V pixels per lane, two walks over their
+// columns (running max + rescaled sum, then the normalised exponentials).  Stock PyTorch runs a negation kernel plus a
+// strided softmax (0.24 ms at [1,193,240,624]).  V = 4 (HW % 4 == 0, 16-byte aligned volumes): 16-byte requests, which reach
+// ~4.5 TB/s on this chip against ~2 TB/s for the 4-byte ones of V = 1 (scripts/ubench/stream_patterns.hip) -- and these
+// kernels are pure streaming.  U planes in flight per walk: 8 of one pixel or 4 of four.  The running maximum is rescaled
+// once per chunk, so U is part of the result's bits: it stays what each width has had.
+template <int V>
+__global__ void __launch_bounds__(256)
 softmin_fwd(const float *__restrict__ x, float *__restrict__ y, int N, int Dn, i64 HW)
 {
-  const i64 total = (i64)N * HW;
+  constexpr int U = V == 1 ? 8 : 4, SH = V == 4 ? 2 : 0;
+  const i64 total = (i64)N * (HW >> SH);
   const i64 stride = (i64)gridDim.x * blockDim.x;
   for (i64 o = (i64)blockIdx.x * blockDim.x + threadIdx.x; o < total; o += stride) {
-    const i64 n = o / HW, pix = o - n * HW;
+    const i64 n = o / (HW >> SH), pix = (o - n * (HW >> SH)) << SH;
     const float *xp = x + n * Dn * HW + pix;
     float *yp = y + n * Dn * HW + pix;
-    float m = -INFINITY, ssum = 0.f;
-    for (int d0 = 0; d0 < Dn; d0 += 8) {
-      float v[8];
+    float m[V], ssum[V], inv[V];
 #pragma unroll
-      for (int u = 0; u < 8; u++) v[u] = -xp[(i64)(d0 + u < Dn ? d0 + u : Dn - 1) * HW];
-      float mc = m;
+    for (int j = 0; j < V; j++) { m[j] = -INFINITY; ssum[j] = 0.f; }
+    for (int d0 = 0; d0 < Dn; d0 += U) {
+      float v[U][V];
+      load_planes(xp, d0, Dn, HW, v);
 #pragma unroll
-      for (int u = 0; u < 8; u++)
-        if (d0 + u < Dn) mc = fmaxf(mc, v[u]);
-      ssum *= expf(m - mc);                   // (exp(-inf) = 0 on the first chunk)
+      for (int j = 0; j < V; j++) {
+        float mc = m[j];
 #pragma unroll
-      for (int u = 0; u < 8; u++)
-        if (d0 + u < Dn) ssum += expf(v[u] - mc);
-      m = mc;
+        for (int u = 0; u < U; u++)
+          if (d0 + u < Dn) mc = fmaxf(mc, -v[u][j]);
+        ssum[j] *= expf(m[j] - mc);                   // (exp(-inf) = 0 on the first chunk)
+#pragma unroll
+        for (int u = 0; u < U; u++)
+          if (d0 + u < Dn) ssum[j] += expf(-v[u][j] - mc);
+        m[j] = mc;
+      }
     }
-    const float inv = 1.f / ssum;
-    for (int d0 = 0; d0 < Dn; d0 += 8) {
-      float v[8];
 #pragma unroll
-      for (int u = 0; u < 8; u++) v[u] = -xp[(i64)(d0 + u < Dn ? d0 + u : Dn - 1) * HW];
+    for (int j = 0; j < V; j++) inv[j] = 1.f / ssum[j];
+    for (int d0 = 0; d0 < Dn; d0 += U) {
+      float v[U][V];
+      load_planes(xp, d0, Dn, HW, v);
 #pragma unroll
-      for (int u = 0; u < 8; u++)
-        if (d0 + u < Dn) yp[(i64)(d0 + u) * HW] = expf(v[u] - m) * inv;
+      for (int u = 0; u < U; u++)
+        if (d0 + u < Dn) {
+          float r[V];
+#pragma unroll
+          for (int j = 0; j < V; j++) r[j] = expf(-v[u][j] - m[j]) * inv[j];
+          st_store<st_f32, V>(yp + (i64)(d0 + u) * HW, r);
+        }
     }
   }
 }
 
+// Two kernels, not softmin_bwd<V>: the folded 4-wide form needed more registers (7 waves per SIMD instead of 8) and ran at
+// 0.164 against 0.121 ms at [1,193,240,624] (profiles/r18a_*), so these stay as they were.
 // gx = -y * (gy - sum_d gy*y)
 static __global__ void __launch_bounds__(256)
 softmin_bwd(const float *__restrict__ y, const float *__restrict__ gy, float *__restrict__ gx, int N, int Dn, i64 HW)
@@ -429,55 +443,7 @@ softmin_bwd(const float *__restrict__ y, const float *__restrict__ gy, float *__
   }
 }
 
-// Four consecutive pixels per lane (16-byte requests, HW % 4 == 0, 16-byte aligned volumes): the same two walks.  The
-// one-pixel forms above issue 4-byte requests, which reach ~2 TB/s on this chip against ~4.5 TB/s for 16-byte ones
-// (scripts/ubench/stream_patterns.hip) -- and these kernels are pure streaming.
-static __global__ void __launch_bounds__(256)
-softmin_fwd4(const float *__restrict__ x, float *__restrict__ y, int N, int Dn, i64 HW)
-{
-  const i64 total = (i64)N * (HW >> 2);
-  const i64 stride = (i64)gridDim.x * blockDim.x;
-  for (i64 o = (i64)blockIdx.x * blockDim.x + threadIdx.x; o < total; o += stride) {
-    const i64 n = o / (HW >> 2), pix = (o - n * (HW >> 2)) << 2;
-    const float *xp = x + n * Dn * HW + pix;
-    float *yp = y + n * Dn * HW + pix;
-    float m[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY}, ssum[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int d0 = 0; d0 < Dn; d0 += 4) {
-      f4 v[4];
-#pragma unroll
-      for (int u = 0; u < 4; u++) v[u] = *reinterpret_cast<const f4 *>(xp + (i64)(d0 + u < Dn ? d0 + u : Dn - 1) * HW);
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        float mc = m[j];
-#pragma unroll
-        for (int u = 0; u < 4; u++)
-          if (d0 + u < Dn) mc = fmaxf(mc, -f4_get(v[u], j));
-        ssum[j] *= expf(m[j] - mc);
-#pragma unroll
-        for (int u = 0; u < 4; u++)
-          if (d0 + u < Dn) ssum[j] += expf(-f4_get(v[u], j) - mc);
-        m[j] = mc;
-      }
-    }
-    float inv[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) inv[j] = 1.f / ssum[j];
-    for (int d0 = 0; d0 < Dn; d0 += 4) {
-      f4 v[4];
-#pragma unroll
-      for (int u = 0; u < 4; u++) v[u] = *reinterpret_cast<const f4 *>(xp + (i64)(d0 + u < Dn ? d0 + u : Dn - 1) * HW);
-#pragma unroll
-      for (int u = 0; u < 4; u++)
-        if (d0 + u < Dn) {
-          f4 r;
-          r.x = expf(-v[u].x - m[0]) * inv[0]; r.y = expf(-v[u].y - m[1]) * inv[1];
-          r.z = expf(-v[u].z - m[2]) * inv[2]; r.w = expf(-v[u].w - m[3]) * inv[3];
-          *reinterpret_cast<f4 *>(yp + (i64)(d0 + u) * HW) = r;
-        }
-    }
-  }
-}
-
+// the same with four consecutive pixels per lane, 4 planes in flight
 static __global__ void __launch_bounds__(256)
 softmin_bwd4(const float *__restrict__ y, const float *__restrict__ gy, float *__restrict__ gx, int N, int Dn, i64 HW)
 {
@@ -589,6 +555,8 @@ softmin_regression_bwd(const float *__restrict__ x, const float *__restrict__ ou
 //                                                  on t = bn(conv) as PyTorch computed it (training mode).
 // Stock PyTorch: batch_norm (r V, w V) + add_ (r 2V, w V) + relu_ (r V, w V) = 7 V; here 2 V in, 1 V out.  y may BE t (the
 // reference adds in place as well), which is why neither carries __restrict__.  blockIdx.y = slice (n, c): no division per element.
+// Two bodies under `if (VEC4)`, not one loop over float[V]: the folded scalar forms ran 0.1 % (forward) and 0.7 % (adjoint) behind
+// these at [1,32,65,80,208] + one element (profiles/r18a_*), outside the spread of five rounds, so these stay as they were.
 template <bool VEC4>
 __global__ void __launch_bounds__(256)
 residual_relu_fwd(const float *t, const float *__restrict__ rem, const float *__restrict__ scale,

@@ -13,7 +13,8 @@
 //                           bn_affine_apply's grid and slice loop (BnGeom) with eight elements per lane.
 //                           y may BE x where both have one width: a lane reads its eight elements before it writes them.
 //   cost_volume_fwd16       GetCostVolume on 2-byte elements: a copy with zeros, and 0x0000 is zero in both formats -- no type.
-//   l1norm_fwd_mixed        l1norm_fwd with a 16-bit x and fp32 outputs.
+//                           Its scalar twin is misc_kernels.h's cost_volume_fwd<uint16_t>.
+//   l1norm_fwd<KT, Tx>      misc_kernels.h's kernel itself, reading a 16-bit x; fp32 outputs.
 //   cast_kernel             element-wise conversion between any two of f32 / f16 / bf16; the same type is a copy of patterns.
 // Lanes along the fastest axis, 64-bit offsets, grid-stride.  V = 8: 16-byte requests (sizes a multiple of 8 and 16-byte
 // aligned bases, decided on the host); V = 1: the scalar twin.
@@ -51,29 +52,6 @@ bn_affine_apply_mixed(const typename Tx::T *x, const typename Tr::T *__restrict_
   }
 }
 
-// cost[n,c,i,h,w] = x[n,c,h,w] (c<C) | y[n,c-C,h,w-i] (c>=C) for w>=i, else 0 -- on 2-byte patterns
-static __global__ void __launch_bounds__(256)
-cost_volume_fwd16s(const uint16_t *__restrict__ x, const uint16_t *__restrict__ y, uint16_t *__restrict__ cost,
-                   int N, int C, int Dn, int H, int W)
-{
-  const i64 total = (i64)N * 2 * C * Dn * H * W;
-  const i64 stride = (i64)gridDim.x * blockDim.x;
-  for (i64 o = (i64)blockIdx.x * blockDim.x + threadIdx.x; o < total; o += stride) {
-    const int w = (int)(o % W);
-    i64 r = o / W;
-    const int h = (int)(r % H); r /= H;
-    const int i = (int)(r % Dn); r /= Dn;
-    const int c = (int)(r % (2 * C));
-    const int n = (int)(r / (2 * C));
-    uint16_t v = 0;
-    if (w >= i) {
-      if (c < C) v = x[(((i64)n * C + c) * H + h) * W + w];
-      else v = y[(((i64)n * C + (c - C)) * H + h) * W + (w - i)];
-    }
-    cost[o] = v;
-  }
-}
-
 // eight consecutive columns per lane (W % 8 == 0, x and cost 16-byte aligned): the left image is one 16-byte load, the shifted
 // right-image samples are eight 2-byte loads at any alignment (the counterpart of cost_volume_fwd4), the store is 16 bytes
 static __global__ void __launch_bounds__(256)
@@ -108,39 +86,6 @@ cost_volume_fwd16(const uint16_t *__restrict__ x, const uint16_t *__restrict__ y
     u4 v;
     v.x = e[0] | (e[1] << 16); v.y = e[2] | (e[3] << 16); v.z = e[4] | (e[5] << 16); v.w = e[6] | (e[7] << 16);
     *reinterpret_cast<u4 *>(cost + (q << 3)) = v;
-  }
-}
-
-// l1norm_fwd (misc_kernels.h) on a 16-bit x: the same lane per (n,g,c,pixel), the same sum t = 0 ... K-1, the same clamp, fp32 out
-template <int KT, typename Tx>
-__global__ void __launch_bounds__(256)
-l1norm_fwd_mixed(const uint16_t *__restrict__ x, NormPtrs p, int N, int G, int C, int Krt, i64 HW)
-{
-  const int K = KT > 0 ? KT : Krt;
-  const i64 total = (i64)N * G * C * HW;
-  const i64 stride = (i64)gridDim.x * blockDim.x;
-  for (i64 idx = (i64)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += stride) {
-    const i64 o = idx / HW, pix = idx - o * HW;
-    const int c = (int)(o % C);
-    const int g = (int)((o / C) % G);
-    const i64 n = o / ((i64)C * G);
-    const uint16_t *xin = x + o * K * HW + pix;
-    float *yb = g == 0 ? p.y[0] : g == 1 ? p.y[1] : g == 2 ? p.y[2] : p.y[3];
-    float *yo = yb + (n * C + c) * K * HW + pix;
-    if (KT > 0) {
-      float v[KT > 0 ? KT : 1];
-      float sa = 0.f;
-#pragma unroll
-      for (int t = 0; t < KT; t++) { v[t] = Tx::get(xin[(i64)t * HW]); sa += fabsf(v[t]); }
-      const float sden = fmaxf(sa, GA_NORM_EPS);
-#pragma unroll
-      for (int t = 0; t < KT; t++) yo[(i64)t * HW] = v[t] / sden;
-    } else {
-      float sa = 0.f;
-      for (int t = 0; t < K; t++) sa += fabsf(Tx::get(xin[(i64)t * HW]));
-      const float sden = fmaxf(sa, GA_NORM_EPS);
-      for (int t = 0; t < K; t++) yo[(i64)t * HW] = Tx::get(xin[(i64)t * HW]) / sden;
-    }
   }
 }
 

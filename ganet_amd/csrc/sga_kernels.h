@@ -773,43 +773,31 @@ sga_merge_px4(const float *__restrict__ A0, const float *__restrict__ A1, const 
 // eval-mode BatchNorm3d + ReLU that follow SGA in SGABlock.forward (models/GANet_deep.py:269-271) folded in;
 // no mask, no arg-max (nothing is kept for a backward).  scale == nullptr: plain max.  Elementwise, linear
 // order, 16-byte requests when n % 4 == 0 and the slice size is a multiple of 4.
-template <bool VEC4>
+template <int V>
 __global__ void __launch_bounds__(256)
 sga_merge_infer(const float *__restrict__ A0, const float *__restrict__ A1, const float *__restrict__ A2,
                 const float *__restrict__ A3, float *__restrict__ out, const float *__restrict__ scale,
                 const float *__restrict__ shift, int C, i64 slice /* D*H*W */, i64 n)
 {
+  constexpr int SH = V == 4 ? 2 : 0;
   const i64 stride = (i64)gridDim.x * blockDim.x;
-  if (VEC4) {
-    const i64 n4 = n >> 2;
-    for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-      const i64 e = i << 2;
-      const f4 a = *reinterpret_cast<const f4 *>(A0 + e), b = *reinterpret_cast<const f4 *>(A1 + e);
-      const f4 c_ = *reinterpret_cast<const f4 *>(A2 + e), d = *reinterpret_cast<const f4 *>(A3 + e);
-      float v[4] = {a.x, a.y, a.z, a.w};
-      const float w1[4] = {b.x, b.y, b.z, b.w}, w2[4] = {c_.x, c_.y, c_.z, c_.w}, w3[4] = {d.x, d.y, d.z, d.w};
-      float sc = 1.f, sh = 0.f;
-      if (scale) { const int ch = (int)((e / slice) % C); sc = scale[ch]; sh = shift[ch]; }
+  for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < (n >> SH); i += stride) {
+    const i64 e = i << SH;
+    float v[V], w1[V], w2[V], w3[V];
+    st_load<st_f32, V>(A0 + e, v);
+    st_load<st_f32, V>(A1 + e, w1);
+    st_load<st_f32, V>(A2 + e, w2);
+    st_load<st_f32, V>(A3 + e, w3);
+    float sc = 1.f, sh = 0.f;
+    if (scale) { const int ch = (int)((e / slice) % C); sc = scale[ch]; sh = shift[ch]; }
 #pragma unroll
-      for (int j = 0; j < 4; j++) {
-        if (v[j] < w1[j]) v[j] = w1[j];
-        if (v[j] < w2[j]) v[j] = w2[j];
-        if (v[j] < w3[j]) v[j] = w3[j];
-        if (scale) v[j] = relu_keep_nan(fmaf(v[j], sc, sh));
-      }
-      f4 r; r.x = v[0]; r.y = v[1]; r.z = v[2]; r.w = v[3];
-      *reinterpret_cast<f4 *>(out + e) = r;
+    for (int j = 0; j < V; j++) {
+      if (v[j] < w1[j]) v[j] = w1[j];
+      if (v[j] < w2[j]) v[j] = w2[j];
+      if (v[j] < w3[j]) v[j] = w3[j];
+      if (scale) v[j] = relu_keep_nan(fmaf(v[j], sc, sh));
     }
-  } else {
-    for (i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += stride) {
-      float v = A0[e];
-      const float b = A1[e], c_ = A2[e], d = A3[e];
-      if (v < b) v = b;
-      if (v < c_) v = c_;
-      if (v < d) v = d;
-      if (scale) { const int ch = (int)((e / slice) % C); v = relu_keep_nan(fmaf(v, scale[ch], shift[ch])); }
-      out[e] = v;
-    }
+    st_store<st_f32, V>(out + e, v);
   }
 }
 
@@ -824,12 +812,11 @@ sga_argmax_px(const float *__restrict__ A, uint16_t *__restrict__ kp, int D, i64
     float m = A[vb];
     int k = 0;
     for (int d0 = 1; d0 < D; d0 += 8) {          // 8 loads in flight per lane
-      float a[8];
-#pragma unroll
-      for (int u = 0; u < 8; u++) a[u] = A[vb + (i64)(d0 + u < D ? d0 + u : D - 1) * HW];
+      float a[8][1];
+      load_planes(A + vb, d0, D, HW, a);
 #pragma unroll
       for (int u = 0; u < 8; u++)
-        if (d0 + u < D && m < a[u]) { m = a[u]; k = d0 + u; }
+        if (d0 + u < D && m < a[u][0]) { m = a[u][0]; k = d0 + u; }
     }
     kp[pidx] = (uint16_t)k;
   }

@@ -17,6 +17,11 @@
 
 namespace ga {
 
+// The wave-wide kernels below take every D <= 72 before with_row_dpl sees it, so a 16-lane kernel with fewer than five
+// disparities per lane (D <= 48) has a caller only in a build that switches them off or runs several rows per wavefront.
+constexpr bool row16_fwd_reached(int dpl) { return dpl >= 5 || !GA_ROW_GD64 || ROW_LN_F != 1; }
+constexpr bool row16_bwdg_reached(int dpl) { return dpl >= 5 || !GA_ROW_BWDG_GD64 || ROW_LN_B != 1; }
+
 // D <= 72 with the depth axis over the whole wavefront: one disparity per lane up to 64, two up to 72.  f(int_c<P>, int_c<NP>):
 // NP = staged pieces per lane = ceil(D_max / 8) of the range: the models' 33 / 48 / 65 get exactly what they need, the ranges in
 // between share an instantiation (12 / 16 pieces for D <= 96 / 128 spill at these register caps: those depths keep the 16-lane kernels)
@@ -59,7 +64,8 @@ void launch_row_fwd(const float *x, const float *g, float *A, int S, int D, int 
 #endif
   with_row_dpl(dpl, [&](auto P) {
     with_flags([&](auto desc, auto fl) {
-      GA_LAUNCH_SMEM((sga_row_fwd<decltype(P)::value, ROW_SBH_F, ROW_PAD_F, ROW_LN_F, decltype(desc)::value, decltype(fl)::value>), grid, block, smem, st, x, g, A, geo);
+      if constexpr (row16_fwd_reached(decltype(P)::value))
+        GA_LAUNCH_SMEM((sga_row_fwd<decltype(P)::value, ROW_SBH_F, ROW_PAD_F, ROW_LN_F, decltype(desc)::value, decltype(fl)::value>), grid, block, smem, st, x, g, A, geo);
     }, dir == 3, full);
   });
 }
@@ -86,7 +92,8 @@ void launch_row_bwdg(const float *g, const uint8_t *mask, const uint16_t *kp, co
   with_row_dpl(dpl, [&](auto P) {
     with_flags([&](auto desc, auto fl) {
       constexpr bool FL = decltype(fl)::value && (decltype(P)::value == 3 || decltype(P)::value == 5);
-      GA_LAUNCH_SMEM((sga_row_bwdg<decltype(P)::value, ROW_SBH_B, ROW_PAD_B, ROW_LN_B, decltype(desc)::value, FL>), grid, block, smem, st, g, mask, kp, gout, G, geo, dir);
+      if constexpr (row16_bwdg_reached(decltype(P)::value))
+        GA_LAUNCH_SMEM((sga_row_bwdg<decltype(P)::value, ROW_SBH_B, ROW_PAD_B, ROW_LN_B, decltype(desc)::value, FL>), grid, block, smem, st, g, mask, kp, gout, G, geo, dir);
     }, dir == 2, full);
   });
 }

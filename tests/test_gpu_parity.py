@@ -116,6 +116,19 @@ def test_sga_horizontal_depth_over_wavefront_boundaries(api, dev, port_oracle):
         shape = (1, 2, D, 3, 104)
         x, gs, go = pc.sga_inputs(shape, seed=100 + D)
         pc.check_sga_forward_backward(api, dev, x, gs, go, _oracle_want(port_oracle, x, gs, go))
+    # the last depth of a range of disparities per lane whose kernel another family's makes unreachable (tests/test_sim_sga.py,
+    # _LAUNCHER_ARMS): rows at 48, 80, 81; columns at 144, 208 with the wide families off; W % 16 and W % 4 only, H % 4
+    no_wide = {"GANET_SGA_WIDE_SCAN": 0, "GANET_SGA_WIDE_COL": 0}
+    for D in (48, 80, 81, 144, 208):
+        for name, value in (no_wide if D >= 96 else {}).items():
+            api.set_option(name, value)
+        try:
+            for W in (16, 20):
+                x, gs, go = pc.sga_inputs((1, 1, D, 4, W), seed=100 + D + W)
+                pc.check_sga_forward_backward(api, dev, x, gs, go, _oracle_want(port_oracle, x, gs, go))
+        finally:
+            for name in no_wide:
+                api.set_option(name, 1)
 
 
 @pytest.mark.parametrize("rowwave", [0, 1])

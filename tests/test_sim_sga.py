@@ -141,6 +141,12 @@ _LAUNCHER_ARMS = [
     ((1, 1, 17, 2, 4), _FALLBACKS, True),
     ((1, 1, 577, 2, 4), _FALLBACKS, True),
 ]
+# The last depth of a range of disparities per lane, where the launchers compile an instantiation out because a better family
+# takes the depth first: rows at 48 (the wave-wide row kernels end at 72, before the 16-lane ones see 1 - 3 per lane), 80 and 81
+# (5 | 9 per lane); columns at 144 and 208 (9 | 13 per lane: beyond the column blocks' 64 KB of LDS, so segments -- with the wide
+# families off, which would take these few scanlines first).  W % 16 and W % 4 only, H % 4 for the tiled workspace.
+_NO_WIDE = {"GANET_SGA_WIDE_SCAN": 0, "GANET_SGA_WIDE_COL": 0}
+_LAUNCHER_ARMS += [((1, 1, D, 4, W), {} if D < 96 else _NO_WIDE, False) for D in (48, 80, 81, 144, 208) for W in (16, 20)]
 
 
 @pytest.mark.parametrize("shape,options,compat", _LAUNCHER_ARMS, ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else None)
