@@ -75,6 +75,10 @@ _PROTOS = {
     "ganet_bn_apply_forward_mixed": [_P] * 5 + [_I] * 7 + [_P],
     "ganet_cost_volume_forward_16": [_P] * 3 + [_I] * 5 + [_P],
     "ganet_l1_normalize_forward_mixed": [_P] * 5 + [_I] * 7 + [_P],
+    "ganet_bn_train_forward_mixed": [_P] * 10 + [_I] * 9 + [_P],
+    "ganet_bn_train_backward_mixed": [_P] * 12 + [_I] * 7 + [_P],
+    "ganet_cost_volume_backward_16": [_P] * 3 + [_I] * 6 + [_P],
+    "ganet_l1_normalize_backward_mixed": [_P] * 6 + [_I] * 7 + [_P],
     "ganet_stereo_input_workspace": [_I] * 3,
     "ganet_stereo_input_stats": [_P] * 3 + [_I] * 3 + [_P],
     "ganet_stereo_input_apply": [_P] * 5 + [_I] * 9 + [_P],

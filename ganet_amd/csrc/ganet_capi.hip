@@ -10,6 +10,7 @@
 #include "disp_tail_kernels.h"
 #include "disp_conv_kernels.h"
 #include "mixed_kernels.h"
+#include "mixed_train_kernels.h"
 #include "sga_kernels.h"
 #include "sga_row_kernels.h"
 #include "sga_col_kernels.h"
@@ -1890,6 +1891,137 @@ GA_EXPORT int ganet_l1_normalize_forward_mixed(const void *x, float *y0, float *
     });
   });
   return check_launch("l1 normalise forward (mixed)");
+}
+
+// ---- mixed precision, training: batch statistics and the backwards on 16-bit storage (mixed_train_kernels.h) -------------------
+namespace {
+// the three sites of a model under autocast: x 16-bit; y (grad_y) in x's format with an fp32 residual or none, or fp32 with none
+int check_bn_mixed_types(const char *who, const void *rem, int x_type, int rem_type, int y_type)
+{
+  if (!type_code(x_type) || !type_code(rem_type) || !type_code(y_type))
+    return fail(GANET_E_INVALID, "%s: type codes x=%d rem=%d y=%d", who, x_type, rem_type, y_type);
+  if (x_type == GANET_F32) return fail(GANET_E_UNSUPPORTED, "%s: x is fp32: no kernel (all fp32 is ganet_bn_train_*'s case)", who);
+  if (y_type != GANET_F32 && y_type != x_type)
+    return fail(GANET_E_UNSUPPORTED, "%s: no kernel for x=%d y=%d: a 16-bit y has x's format", who, x_type, y_type);
+  if (rem && rem_type != GANET_F32) return fail(GANET_E_UNSUPPORTED, "%s: no kernel for a 16-bit rem (type %d)", who, rem_type);
+  if (rem && y_type == GANET_F32) return fail(GANET_E_UNSUPPORTED, "%s: no kernel for a residual with an fp32 y", who);
+  return GANET_OK;
+}
+}  // namespace
+
+GA_EXPORT int ganet_bn_train_forward_mixed(const void *x, const float *rem, const float *weight, const float *bias,
+                                           float *running_mean, float *running_var, double *workspace, void *y, float *save_mean,
+                                           float *save_invstd, int N, int C, int S, int momentum_bits, int eps_bits, int relu,
+                                           int x_type, int rem_type, int y_type, void *stream)
+{
+  const char *who = "ganet_bn_train_forward_mixed";
+  GA_TRY(check_ptrs(who, x, workspace, y, save_mean, save_invstd));
+  if ((running_mean == nullptr) != (running_var == nullptr)) return fail(GANET_E_INVALID, "%s: running_mean and running_var come together", who);
+  if (y == x || y == (const void *)rem) return fail(GANET_E_INVALID, "%s: y must not alias an input", who);
+  GA_TRY(check_bn_mixed_types(who, rem, x_type, rem_type, y_type));
+  const bool vec = S % MX_V == 0 && aligned16(x, y, rem);
+  BnGeom g;
+  GA_TRY(bn_geom(who, N, C, S, vec ? MX_V : 1, true, &g));
+  const float momentum = bn_float(momentum_bits), eps = bn_float(eps_bits);
+  const dim3 grid(g.Rs * g.Rn, C);
+  hipStream_t st = (hipStream_t)stream;
+  int rc;
+  with_st16(x_type, [&](auto t16) {
+    with_flags([&](auto o16, auto v) {
+      using Tx = typename decltype(t16)::type;
+      using Ty = std::conditional_t<decltype(o16)::value, Tx, st_f32>;
+      constexpr int V = decltype(v)::value ? MX_V : 1;
+      GA_LAUNCH((bn_stat_partials_mixed<Tx, V>), grid, dim3(BN_BLOCK), st, (const typename Tx::T *)x, workspace, g);
+      if ((rc = check_launch("batch norm statistics (mixed)")) != GANET_OK) return;
+      GA_LAUNCH((bn_train_apply_mixed<Tx, Ty, V>), grid, dim3(BN_BLOCK), st, (const typename Tx::T *)x, rem, weight, bias, running_mean,
+                running_var, workspace, (typename Ty::T *)y, save_mean, save_invstd, g, momentum, eps, relu);
+      rc = check_launch("batch norm forward (mixed)");
+    }, y_type != GANET_F32, vec);
+  });
+  return rc;
+}
+
+GA_EXPORT int ganet_bn_train_backward_mixed(const void *x, const float *rem, const void *grad_y, const float *weight,
+                                            const float *bias, const float *save_mean, const float *save_invstd, double *workspace,
+                                            void *grad_x, float *grad_rem, float *grad_weight, float *grad_bias, int N, int C, int S,
+                                            int relu, int x_type, int rem_type, int gy_type, void *stream)
+{
+  const char *who = "ganet_bn_train_backward_mixed";
+  GA_TRY(check_ptrs(who, x, grad_y, save_mean, save_invstd, workspace));
+  for (const void *o : {(const void *)grad_x, (const void *)grad_rem})
+    if (o && (o == x || o == (const void *)rem || o == grad_y)) return fail(GANET_E_INVALID, "%s: a gradient must not alias an input", who);
+  if (grad_x && grad_x == (void *)grad_rem) return fail(GANET_E_INVALID, "%s: grad_x and grad_rem are two buffers", who);
+  GA_TRY(check_bn_mixed_types(who, rem, x_type, rem_type, gy_type));
+  const bool vec = S % MX_V == 0 && aligned16(x, rem, grad_y, grad_x, grad_rem);
+  BnGeom g;
+  GA_TRY(bn_geom(who, N, C, S, vec ? MX_V : 1, true, &g));
+  if (!grad_x && !grad_rem && !grad_weight && !grad_bias) return GANET_OK;
+  const dim3 grid(g.Rs * g.Rn, C), apply_grid = (grad_x || grad_rem) ? grid : dim3(1, C);
+  hipStream_t st = (hipStream_t)stream;
+  int rc;
+  with_st16(x_type, [&](auto t16) {
+    with_flags([&](auto o16, auto v) {
+      using Tx = typename decltype(t16)::type;
+      using Ty = std::conditional_t<decltype(o16)::value, Tx, st_f32>;
+      constexpr int V = decltype(v)::value ? MX_V : 1;
+      const typename Tx::T *xp = (const typename Tx::T *)x;
+      const typename Ty::T *gp = (const typename Ty::T *)grad_y;
+      GA_LAUNCH((bn_bwd_partials_mixed<Tx, Ty, V>), grid, dim3(BN_BLOCK), st, xp, rem, gp, weight, bias, save_mean, save_invstd, workspace, g, relu);
+      if ((rc = check_launch("batch norm backward sums (mixed)")) != GANET_OK) return;
+      GA_LAUNCH((bn_bwd_apply_mixed<Tx, Ty, V>), apply_grid, dim3(BN_BLOCK), st, xp, rem, gp, weight, bias, save_mean, save_invstd, workspace,
+                (typename Tx::T *)grad_x, grad_rem, grad_weight, grad_bias, g, relu);
+      rc = check_launch("batch norm backward (mixed)");
+    }, gy_type != GANET_F32, vec);
+  });
+  return rc;
+}
+
+GA_EXPORT int ganet_cost_volume_backward_16(const void *grad_cost, void *grad_x, void *grad_y, int N, int C, int Dn, int H, int W,
+                                            int type, void *stream)
+{
+  const char *who = "ganet_cost_volume_backward_16";
+  GA_TRY(check_ptrs(who, grad_cost, grad_x, grad_y));
+  GA_TRY(check_positive(who, N, C, Dn, H, W));
+  if (!type_code(type)) return fail(GANET_E_INVALID, "%s: type code %d", who, type);
+  if (type == GANET_F32) return fail(GANET_E_UNSUPPORTED, "%s: fp32: that is ganet_cost_volume_backward's case", who);
+  if (grad_x == grad_cost || grad_y == grad_cost || grad_x == grad_y) return fail(GANET_E_INVALID, "%s: three buffers, none an alias of another", who);
+  const bool vec = W % MX_V == 0 && aligned16(grad_cost, grad_x, grad_y);
+  const i64 n = (i64)N * C * H * W;
+  with_st16(type, [&](auto t16) {
+    with_width<MX_V>(vec, [&](auto v) {
+      constexpr int V = decltype(v)::value;
+      GA_LAUNCH((cost_volume_bwd16<typename decltype(t16)::type, V>), dim3(ew_grid(n / V)), dim3(256), (hipStream_t)stream,
+                (const uint16_t *)grad_cost, (uint16_t *)grad_x, (uint16_t *)grad_y, N, C, Dn, H, W);
+    });
+  });
+  return check_launch("cost volume backward (16-bit)");
+}
+
+GA_EXPORT int ganet_l1_normalize_backward_mixed(const void *x, const float *gy0, const float *gy1, const float *gy2, const float *gy3,
+                                                void *grad_x, int N, int G, int C, int K, int H, int W, int x_type, void *stream)
+{
+  const char *who = "ganet_l1_normalize_backward_mixed";
+  GA_TRY(check_norm(who, N, G, C, K, H, W));
+  const float *gs[4] = {gy0, gy1, gy2, gy3};
+  GA_TRY(check_ptrs(who, x, grad_x));
+  if (!type_code(x_type)) return fail(GANET_E_INVALID, "%s: type code %d", who, x_type);
+  if (x_type == GANET_F32) return fail(GANET_E_UNSUPPORTED, "%s: x is fp32: that is ganet_l1_normalize_backward's case", who);
+  if (grad_x == x) return fail(GANET_E_INVALID, "%s: grad_x must not alias x", who);
+  NormPtrs p = {};
+  for (int g = 0; g < 4; g++) {
+    if (g < G && !gs[g]) return fail(GANET_E_INVALID, "%s: null gradient %d", who, g);
+    p.gy[g] = gs[g < G ? g : 0];
+  }
+  const i64 HW = (i64)H * W;
+  const dim3 grid(ew_grid((i64)N * G * C * HW)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  with_st16(x_type, [&](auto t16) {
+    with_int_else<0, 5, 75>(K, [&](auto KC) {
+      GA_LAUNCH((l1norm_bwd<decltype(KC)::value, typename decltype(t16)::type>), grid, block, st, (const uint16_t *)x, p,
+                (uint16_t *)grad_x, N, G, C, K, HW);
+    });
+  });
+  return check_launch("l1 normalise backward (mixed)");
 }
 
 // ---- image front and back end (predict.py:75-114, :132-138; dataloader/dataset.py:48-92) --------------------------------------

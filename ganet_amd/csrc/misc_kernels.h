@@ -217,10 +217,12 @@ l1norm_fwd(const typename Tx::T *__restrict__ x, NormPtrs p, int N, int G, int C
   }
 }
 
-// adjoint: gx_t = (gy_t - sgn(x_t) * sum_u gy_u y_u) / s  with s = sum|x| (> eps); gy_t / eps where the norm was clamped
-template <int KT>
+// adjoint: gx_t = (gy_t - sgn(x_t) * sum_u gy_u y_u) / s  with s = sum|x| (> eps); gy_t / eps where the norm was clamped.
+// Tx: the storage of x and of gx (fp32, or 16-bit behind a 16-bit convolution: gx is rounded once on its store); the incoming
+// gradients are fp32.
+template <int KT, typename Tx = st_f32>
 __global__ void __launch_bounds__(256)
-l1norm_bwd(const float *__restrict__ x, NormPtrs p, float *__restrict__ gx, int N, int G, int C, int Krt, i64 HW)
+l1norm_bwd(const typename Tx::T *__restrict__ x, NormPtrs p, typename Tx::T *__restrict__ gx, int N, int G, int C, int Krt, i64 HW)
 {
   const int K = KT > 0 ? KT : Krt;
   const i64 total = (i64)N * G * C * HW;
@@ -230,15 +232,15 @@ l1norm_bwd(const float *__restrict__ x, NormPtrs p, float *__restrict__ gx, int 
     const int c = (int)(o % C);
     const int g = (int)((o / C) % G);
     const i64 n = o / ((i64)C * G);
-    const float *xin = x + o * K * HW + pix;
-    float *gxo = gx + o * K * HW + pix;
+    const typename Tx::T *xin = x + o * K * HW + pix;
+    typename Tx::T *gxo = gx + o * K * HW + pix;
     const float *gb = g == 0 ? p.gy[0] : g == 1 ? p.gy[1] : g == 2 ? p.gy[2] : p.gy[3];
     const float *gyi = gb + (n * C + c) * K * HW + pix;
     if (KT > 0) {
       float v[KT > 0 ? KT : 1], gv[KT > 0 ? KT : 1];
       float sa = 0.f, dot = 0.f;
 #pragma unroll
-      for (int t = 0; t < KT; t++) { v[t] = xin[(i64)t * HW]; gv[t] = gyi[(i64)t * HW]; sa += fabsf(v[t]); }
+      for (int t = 0; t < KT; t++) { v[t] = Tx::get(xin[(i64)t * HW]); gv[t] = gyi[(i64)t * HW]; sa += fabsf(v[t]); }
       const bool clamped = sa < GA_NORM_EPS;
       const float sden = fmaxf(sa, GA_NORM_EPS);
 #pragma unroll
@@ -247,19 +249,24 @@ l1norm_bwd(const float *__restrict__ x, NormPtrs p, float *__restrict__ gx, int 
 #pragma unroll
       for (int t = 0; t < KT; t++) {
         const float sg = v[t] > 0.f ? 1.f : (v[t] < 0.f ? -1.f : 0.f);
-        gxo[(i64)t * HW] = (gv[t] - sg * dot) / sden;
+        const float r = (gv[t] - sg * dot) / sden;
+        // (the store is written out here, not through st_store: this form leaves the fp32 instantiation's instruction text as it was)
+        if constexpr (sizeof(typename Tx::T) == 4) gxo[(i64)t * HW] = r;
+        else gxo[(i64)t * HW] = Tx::put(r);
       }
     } else {
       float sa = 0.f, dot = 0.f;
-      for (int t = 0; t < K; t++) sa += fabsf(xin[(i64)t * HW]);
+      for (int t = 0; t < K; t++) sa += fabsf(Tx::get(xin[(i64)t * HW]));
       const bool clamped = sa < GA_NORM_EPS;
       const float sden = fmaxf(sa, GA_NORM_EPS);
-      for (int t = 0; t < K; t++) dot = fmaf(gyi[(i64)t * HW], xin[(i64)t * HW] / sden, dot);
+      for (int t = 0; t < K; t++) dot = fmaf(gyi[(i64)t * HW], Tx::get(xin[(i64)t * HW]) / sden, dot);
       if (clamped) dot = 0.f;
       for (int t = 0; t < K; t++) {
-        const float xv = xin[(i64)t * HW];
+        const float xv = Tx::get(xin[(i64)t * HW]);
         const float sg = xv > 0.f ? 1.f : (xv < 0.f ? -1.f : 0.f);
-        gxo[(i64)t * HW] = (gyi[(i64)t * HW] - sg * dot) / sden;
+        const float r = (gyi[(i64)t * HW] - sg * dot) / sden;
+        if constexpr (sizeof(typename Tx::T) == 4) gxo[(i64)t * HW] = r;      // (as above)
+        else gxo[(i64)t * HW] = Tx::put(r);
       }
     }
   }

@@ -1,12 +1,14 @@
-"""Mixed-precision inference modules (opt-in; see ganet_amd.functions.mixed): 16-bit storage between MIOpen's 16-bit
-convolutions and the fp32 guided-aggregation ops.  Nothing here changes BnRelu, GetCostVolume or any other existing module."""
+"""Mixed-precision modules (opt-in; see ganet_amd.functions.mixed and .mixed_train): 16-bit storage between MIOpen's 16-bit
+convolutions and the fp32 guided-aggregation ops.  MixedBnRelu / MixedGetCostVolume are the inference forms; MixedTrainBnRelu /
+MixedTrainGetCostVolume carry gradients.  Nothing here changes BnRelu, GetCostVolume or any other existing module."""
 import torch
 from torch.nn.modules.module import Module
 
 from ..functions.mixed import bn_apply_mixed, cost_volume_16
+from ..functions.mixed_train import CostVolume16Function, MixedBnReluFunction
 from .fused import folded_bn
 
-__all__ = ["MixedBnRelu", "MixedGetCostVolume"]
+__all__ = ["MixedBnRelu", "MixedGetCostVolume", "MixedTrainBnRelu", "MixedTrainGetCostVolume"]
 
 
 class MixedBnRelu(Module):
@@ -57,3 +59,48 @@ class MixedGetCostVolume(Module):
 
     def forward(self, x, y):
         return cost_volume_16(x.contiguous(), y.contiguous(), self.maxdisp)
+
+
+class MixedTrainBnRelu(Module):
+    """BnRelu for a 16-bit input under torch.autocast, with gradients: forward(x, rem=None) == relu(bn(x) + rem).
+      training mode  batch statistics on the 16-bit x, fp32 / fp64 arithmetic, one rounding to the output's dtype, two launches
+                     forward and two backward (MixedBnReluFunction); `bn`'s running buffers and num_batches_tracked are updated
+                     as _BatchNorm.forward updates them.  x fp16 | bf16 [N,C,*]; rem None or fp32 (an SGABlock's input, and then
+                     the output has x's dtype); out_dtype None (x's dtype) or torch.float32 in front of an fp32 op (SGA).
+                     momentum=None (the cumulative average needs a host read of the batch counter) has no fused path: it raises.
+      eval mode      MixedBnRelu's fold, with MixedBnRelu's refusals."""
+
+    def __init__(self, bn, relu=True, out_dtype=None):
+        super().__init__()
+        if not isinstance(bn, torch.nn.modules.batchnorm._BatchNorm):
+            raise TypeError("MixedTrainBnRelu wraps a BatchNorm2d / BatchNorm3d")
+        if out_dtype not in (None, torch.float32, torch.float16, torch.bfloat16):
+            raise TypeError(f"MixedTrainBnRelu: out_dtype is None, torch.float32 or the input's dtype, got {out_dtype}")
+        self.bn = bn                      # the caller's BatchNorm (shared, not copied)
+        self.relu = relu
+        self.out_dtype = out_dtype
+        object.__setattr__(self, "_eval", MixedBnRelu(bn, relu, out_dtype, inplace=False))     # (not a second registration of bn)
+
+    def forward(self, x, rem=None):
+        bn = self.bn
+        if not (bn.training or not bn.track_running_stats):
+            return self._eval(x, rem)
+        if bn.track_running_stats and bn.momentum is None:
+            raise RuntimeError("MixedTrainBnRelu: momentum=None (a cumulative average) has no fused path; give the BatchNorm a momentum")
+        if bn.training and bn.track_running_stats and bn.num_batches_tracked is not None:
+            bn.num_batches_tracked.add_(1)
+        running = (bn.running_mean, bn.running_var) if bn.training and bn.track_running_stats else (None, None)
+        return MixedBnReluFunction.apply(x.contiguous(), rem.contiguous() if rem is not None else None, bn.weight, bn.bias, *running,
+                                         bn.momentum if bn.momentum is not None else 0.0, bn.eps, self.relu, self.out_dtype)
+
+
+class MixedTrainGetCostVolume(Module):
+    """MixedGetCostVolume with gradients: forward(x, y) [N,C,H,W] 16-bit -> [N,2C,maxdisp+1,H,W] of the same dtype; the backward
+    sums in fp32 and rounds once (CostVolume16Function)."""
+
+    def __init__(self, maxdisp):
+        super().__init__()
+        self.maxdisp = int(maxdisp) + 1   # planes, as GetCostVolume counts them
+
+    def forward(self, x, y):
+        return CostVolume16Function.apply(x.contiguous(), y.contiguous(), self.maxdisp)

@@ -22,18 +22,20 @@ use_fused_disp_conv (opt-in, composes with all of the above in any order):
                                                    forward its owner has calls it
 use_mixed_precision (opt-in, inference; applies use_fused_ops and use_fused_bn where they have not been):
   every site between a convolution and a guided-aggregation op on 16-bit storage, for torch.autocast: see the function
+use_mixed_precision_training (opt-in): the same sites bound to forms that carry gradients, for a training step under autocast
 """
 import types
 
 import torch
 
 from ganet_amd.functions import mixed as mixed_fn
+from ganet_amd.functions import mixed_train as mixed_train_fn
 from ganet_amd.functions.fused import (LgaRegressFunction, SoftminFunction, normalize_filters, normalize_guidance,
                                        sga_forward_infer)
-from ganet_amd.functions.GANet import Lga2Function, LgaFunction
+from ganet_amd.functions.GANet import Lga2Function, LgaFunction, SgaFunction
 from ganet_amd.modules.fused import (BnRelu, DispAggTail, DispConv, DispTail, GuidedSGA, GuidedSGABnRelu, ResidualBnRelu, SoftminDisparityRegression,
                                      TrilinearUpsample, folded_bn)
-from ganet_amd.modules.mixed import MixedBnRelu
+from ganet_amd.modules.mixed import MixedBnRelu, MixedTrainBnRelu
 
 _UP = TrilinearUpsample()
 
@@ -339,6 +341,148 @@ def use_mixed_precision(model, dtype=torch.bfloat16, kernels=True):
                     and isinstance(seq[1], torch.nn.ReLU):
                 object.__setattr__(seq, "_mixed_bn", _TopBnRelu(seq[0], mx.kernels))
                 seq.forward = types.MethodType(_mixed_top_bn_relu_forward, seq)
+                n += 1
+    return n
+
+
+# ---- mixed precision, training: the same sites bound to forms that carry gradients ----------------------------------------------------
+
+class _MixedTrainOps:
+    """_MixedOps for training: the 16-bit-storage Functions of ganet_amd.functions.mixed_train (kernels=True) or the cast arm --
+    the existing fp32 op between ATen casts, with autograd through both (kernels=False)"""
+
+    def __init__(self, kernels):
+        self.kernels = bool(kernels)
+
+    def bn(self, bn, relu, out_dtype=None):
+        return MixedTrainBnRelu(bn, relu=relu, out_dtype=out_dtype) if self.kernels else _CastArmBnRelu(bn, relu, out_dtype)
+
+    def cast(self, t, dtype):
+        return mixed_train_fn.CastFunction.apply(t.contiguous(), dtype) if self.kernels else t.to(dtype)
+
+    def guidance(self, g, channels):
+        if self.kernels:
+            return mixed_train_fn.NormalizeGuidanceMixedFunction.apply(g.contiguous(), channels)
+        return normalize_guidance(g.float(), channels)
+
+    def filters(self, g):
+        return mixed_train_fn.NormalizeFiltersMixedFunction.apply(g.contiguous()) if self.kernels else normalize_filters(g.float())
+
+    def cost_volume(self, cv, x, y):
+        if self.kernels:
+            return mixed_train_fn.CostVolume16Function.apply(x.contiguous(), y.contiguous(), cv.maxdisp)   # (the module holds maxdisp + 1)
+        return type(cv).forward(cv, x.float(), y.float()).to(x.dtype)
+
+
+def _mixed_train_basicconv_forward(self, x):
+    t = self.conv(x)
+    return self._mixed_bn(t) if t.dtype in _HALF else self._fused_bn(t)
+
+
+def _mixed_train_sgablock_forward(self, x, g):
+    if g.dtype not in _HALF:
+        return _sgablock_forward(self, x, g)
+    mx = self._mixed
+    if x.dtype != torch.float32:          # (a producer this file does not know: SGA is fp32)
+        x = mx.cast(x, torch.float32)
+    rem = x
+    ks = mx.guidance(g, x.shape[1])       # 16-bit guidance -> four fp32 weight volumes; the gradient comes back in 16 bits
+    x = SgaFunction.apply(x.contiguous(), *ks)        # GuidedSGA's path: fp32 in and out, with its backward
+    if not self.refine:
+        return self._fused_tail(x, rem)
+    x = self._mixed_bnrelu(x)             # bn_relu behind SGA: fp32 in and out, BnRelu's training kernels on both arms
+    x = self.conv_refine.conv(x)          # autocast rounds the fp32 volume for the convolution (a 16-bit SGA epilogue is out of scope)
+    return self._mixed_tail(x, rem) if x.dtype in _HALF else self._fused_tail(x, rem)
+
+
+def _mixed_train_top_bn_relu_forward(self, x):
+    # GANet.bn_relu behind the bilinear up-sampling: fp32 in, 16-bit out.  2-D and small: the cast arm on both settings of `kernels`
+    if x.is_cuda and x.dtype == torch.float32 and torch.is_autocast_enabled("cuda"):
+        return self._mixed_bn(x).to(torch.get_autocast_dtype("cuda"))
+    if x.dtype in _HALF:
+        return self._mixed_bn(x.float()).to(x.dtype)
+    return type(self).forward(self, x)
+
+
+def _mixed_train_dispagg_forward(self, x, lg1, lg2):
+    mx, tail = self._mixed, self._fused_tail
+    v = torch.squeeze(_UP(_conv32x1_f32(self, x), _up_size(self, x)), 1)
+    if lg1.dtype not in _HALF:
+        return tail(v, lg1, lg2)
+    assert lg1.size() == lg2.size()
+    f1, f2 = mx.filters(lg1), mx.filters(lg2)
+    v = Lga2Function.apply(v, f1, tail.radius)                        # DispAggTail.forward on filters normalised from 16 bits
+    v = SoftminFunction.apply(v.contiguous())
+    v = LgaFunction.apply(v, f2, tail.radius)
+    return LgaRegressFunction.apply(v, f2, tail.radius, tail.ndisp)
+
+
+def use_mixed_precision_training(model, dtype=torch.bfloat16, kernels=True):
+    """Prepares GANet_deep / GANet11 for TRAINING under torch.autocast("cuda", dtype=dtype) -- harness.steps.train_step(..., amp=dtype):
+    the sites of use_mixed_precision, bound to forms that carry gradients (ganet_amd.modules.mixed.MixedTrain*, functions.mixed_train).
+    The fp32 SGA / LGA / tail Functions, DispConv, DispTail and the loss stay what they are.  Applies use_fused_ops and
+    use_fused_bn first where the model has not been rebound; helpers stay out of the module tree (no state_dict key moves).
+      BasicConv (use_bn)   a 16-bit convolution output -> MixedTrainBnRelu (batch statistics on 16-bit storage in training mode,
+                           MixedBnRelu's fold in eval mode); fp32 (autocast off) -> the BnRelu it had
+      ... in front of an SGABlock (the producers of _SGA_PRODUCER, as in use_mixed_precision): out_dtype fp32 -- SGA's x
+      SGABlock             guidance through NormalizeGuidanceMixedFunction, SGA on SgaFunction (GuidedSGA's path), bn_relu on BnRelu
+                           (fp32 in and out: no cast stands there, so both settings of `kernels` share it), the tail
+                           MixedTrainBnRelu(t 16-bit, rem fp32) -> 16-bit
+      GANet.cv             CostVolume16Function
+      Disp / DispAgg       conv32x1's small output up-cast by CastFunction; filters through NormalizeFiltersMixedFunction
+      GANet.conv_refine    its small 16-bit output up-cast by CastFunction in front of the bilinear up-sampling
+      GANet.bn_relu        fp32 in, 16-bit out: the cast arm (BnRelu, then .to) -- 2-D and small; a fourth type combination of the
+                           training kernels is out of scope
+    kernels=False binds every site to the cast arm: the existing fp32 op on .float() inputs followed by .to(out_dtype), with
+    autograd -- the fallback, the tests' yardstick and the baseline of the measurement.  Returns the number of sites."""
+    if dtype not in _HALF:
+        raise TypeError(f"use_mixed_precision_training: dtype is torch.bfloat16 or torch.float16, got {dtype}")
+    mods = list(model.modules())
+    if not any("_fused_sga" in m.__dict__ for m in mods if type(m).__name__ == "SGABlock"):
+        use_fused_ops(model)
+    if not any("_fused_bn" in m.__dict__ for m in mods if type(m).__name__ == "BasicConv"):
+        use_fused_bn(model)
+    mx = _MixedTrainOps(kernels)
+    to_f32 = set()
+    for m in mods:
+        if type(m).__name__ == "CostAggregation":
+            for sga, producer in _SGA_PRODUCER.items():
+                p = getattr(m, producer, None)
+                if hasattr(m, sga) and p is not None:
+                    to_f32.add(id(p.conv2 if type(p).__name__ == "Conv2x" else p))
+    n = 0
+    for m in mods:
+        kind = type(m).__name__
+        # (object.__setattr__: the helpers stay out of the module tree, state_dict keys do not move)
+        if kind == "BasicConv" and m.use_bn:
+            object.__setattr__(m, "_mixed_bn", mx.bn(m.bn, bool(m.relu), torch.float32 if id(m) in to_f32 else None))
+            m.forward = types.MethodType(_mixed_train_basicconv_forward, m)
+            n += 1
+        elif kind == "SGABlock":
+            object.__setattr__(m, "_mixed", mx)
+            object.__setattr__(m, "_mixed_tail", mx.bn(m.conv_refine.bn if m.refine else m.bn, True))
+            if m.refine:
+                object.__setattr__(m, "_mixed_bnrelu", BnRelu(m.bn_relu[0], relu=True))
+            m.forward = types.MethodType(_mixed_train_sgablock_forward, m)
+            n += 1
+        elif kind == "GetCostVolume":
+            object.__setattr__(m, "_mixed", mx)
+            m.forward = types.MethodType(_mixed_cv_forward, m)
+            n += 1
+        elif kind in ("Disp", "DispAgg"):
+            object.__setattr__(m, "_mixed", mx)
+            m.forward = types.MethodType(_mixed_train_dispagg_forward if kind == "DispAgg" else _mixed_disp_forward, m)
+            n += 1
+        elif kind == "GANet":
+            conv, seq = getattr(m, "conv_refine", None), getattr(m, "bn_relu", None)
+            if isinstance(conv, torch.nn.Conv2d):
+                object.__setattr__(conv, "_mixed", mx)
+                conv.forward = types.MethodType(_mixed_top_conv_forward, conv)
+                n += 1
+            if isinstance(seq, torch.nn.Sequential) and len(seq) == 2 and isinstance(seq[0], torch.nn.modules.batchnorm._BatchNorm) \
+                    and isinstance(seq[1], torch.nn.ReLU):
+                object.__setattr__(seq, "_mixed_bn", BnRelu(seq[0], relu=True))
+                seq.forward = types.MethodType(_mixed_train_top_bn_relu_forward, seq)
                 n += 1
     return n
 

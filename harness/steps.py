@@ -57,8 +57,11 @@ def loss_mix(name, outputs, target, mask, crit):
     return 0.2 * l1(disp0) + 0.6 * l1(disp1) + crit(disp2[mask], target[mask])
 
 
-def train_step(model, optimizer, name, left, right, target, max_disp, crit, fused_loss=None):
+def train_step(model, optimizer, name, left, right, target, max_disp, crit, fused_loss=None, amp=None, scaler=None):
     """One optimisation step (train.py:85-120).  Returns (loss, mean abs error of the last disparity).
+    amp: torch.bfloat16 | torch.float16 runs the forward under torch.autocast("cuda", dtype=amp) -- the convolutions in 16 bits --
+    for a model prepared by harness.fuse.use_mixed_precision_training; the two images are rounded to `amp` once, by ganet_cast.
+    scaler: a torch.amp.GradScaler (fp16): the loss is scaled for the backward and the step goes through scaler.step / update.
     fused_loss: a ganet_amd.modules.fused.DisparityLoss built for this model and max_disp; the loss mix and the error then
     come from its one op (`name` and `crit` are not used), and a rank without a valid pixel needs no branch of its own: with
     a count of zero the op returns loss 0 and its backward hands all-zero gradients to every output."""
@@ -76,7 +79,14 @@ def train_step(model, optimizer, name, left, right, target, max_disp, crit, fuse
     if total == 0:
         return None, None
     optimizer.zero_grad()
-    outputs = model(left, right)
+    if amp is None:
+        outputs = model(left, right)
+    else:
+        if left.is_cuda and left.dtype == torch.float32 and right.dtype == torch.float32:
+            from ganet_amd.functions.mixed import cast
+            left, right = cast(left.contiguous(), amp), cast(right.contiguous(), amp)
+        with torch.autocast("cuda", dtype=amp):
+            outputs = model(left, right)
     if fused_loss is not None:
         loss, stats = fused_loss(outputs, target)
         err = stats[fused_loss.epe_index].detach()
@@ -90,7 +100,7 @@ def train_step(model, optimizer, name, left, right, target, max_disp, crit, fuse
     else:
         loss = loss_mix(name, outputs, target, mask, crit)
         err = torch.mean(torch.abs(outputs[-1][mask] - target[mask])).detach()
-    loss.backward()
+    (scaler.scale(loss) if scaler is not None else loss).backward()
     if multi and n_empty:
         # a non-finite activation on a zero-weighted rank has reached everybody's averaged gradients by now: the step is skipped
         # by a COLLECTIVE decision (the averaged gradients are the same on every rank; the flag is reduced all the same, so that
@@ -102,7 +112,11 @@ def train_step(model, optimizer, name, left, right, target, max_disp, crit, fuse
         if int(bad):
             optimizer.zero_grad()
             return loss.detach(), err
-    optimizer.step()
+    if scaler is not None:
+        scaler.step(optimizer)            # (skips the step by itself where a scaled gradient is not finite)
+        scaler.update()
+    else:
+        optimizer.step()
     return loss.detach(), err
 
 

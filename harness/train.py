@@ -48,6 +48,9 @@ def parse(argv=None):
     ap.add_argument("--fused_bn", action="store_true", help="BatchNorm + ReLU behind every BasicConv on ganet_amd.modules.fused.BnRelu")
     ap.add_argument("--fused_disp", action="store_true", help="every Disp behind its conv32x1 on ganet_amd.modules.fused.DispTail (no up-sampled volume)")
     ap.add_argument("--fused_conv32", action="store_true", help="conv32x1 of every Disp / DispAgg on ganet_amd.modules.fused.DispConv (HIP kernels instead of MIOpen)")
+    ap.add_argument("--amp", default="", choices=["", "bf16", "fp16"],
+                    help="run the step under torch.autocast on a model prepared by harness.fuse.use_mixed_precision_training (fp16: with a GradScaler)")
+    ap.add_argument("--amp_cast_arm", action="store_true", help="with --amp: bind every mixed-precision site to the cast arm (kernels=False)")
     ap.add_argument("--kernel_share", action="store_true", help="add the per-group device-time table (torch.profiler over 2 extra steps, rank 0)")
     ap.add_argument("--resume", default="")
     ap.add_argument("--save", default="")
@@ -73,6 +76,11 @@ def run(args, hook=None):
     n_fused_bn = fuse.use_fused_bn(steps.unwrap(model)) if args.fused_bn else 0
     n_fused_disp = fuse.use_fused_disp_tail(steps.unwrap(model)) if args.fused_disp else 0
     n_fused_conv32 = fuse.use_fused_disp_conv(steps.unwrap(model)) if args.fused_conv32 else 0
+    amp = {"": None, "bf16": torch.bfloat16, "fp16": torch.float16}[getattr(args, "amp", "")]
+    if amp is not None and cpu:
+        raise SystemExit("--amp needs --device cuda")
+    n_amp = fuse.use_mixed_precision_training(steps.unwrap(model), amp, kernels=not args.amp_cast_arm) if amp is not None else 0
+    scaler = torch.amp.GradScaler("cuda") if amp == torch.float16 else None
     opt = torch.optim.Adam(model.parameters(), lr=args.lr, betas=(0.9, 0.999))
     epoch0 = 0
     if args.resume:
@@ -88,13 +96,13 @@ def run(args, hook=None):
     sync = (lambda: None) if cpu else torch.cuda.synchronize
     losses = []
     for _ in range(args.warmup):
-        steps.train_step(model, opt, args.model, left, right, target, args.max_disp, crit, fused_loss)
+        steps.train_step(model, opt, args.model, left, right, target, args.max_disp, crit, fused_loss, amp=amp, scaler=scaler)
     if not cpu:
         torch.cuda.reset_peak_memory_stats()
 
     def timed():
         for _ in range(args.steps):
-            loss, err = steps.train_step(model, opt, args.model, left, right, target, args.max_disp, crit, fused_loss)
+            loss, err = steps.train_step(model, opt, args.model, left, right, target, args.max_disp, crit, fused_loss, amp=amp, scaler=scaler)
             if loss is not None:      # (a step every rank skipped: no valid pixel anywhere)
                 losses.append(float(loss))
 
@@ -102,7 +110,7 @@ def run(args, hook=None):
     share = None
     if args.kernel_share and ctx.rank == 0 and not cpu and ctx.world_size == 1:
         from harness.kernel_share import profile_passes
-        share = profile_passes(lambda: steps.train_step(model, opt, args.model, left, right, target, args.max_disp, crit, fused_loss), 2)
+        share = profile_passes(lambda: steps.train_step(model, opt, args.model, left, right, target, args.max_disp, crit, fused_loss, amp=amp, scaler=scaler), 2)
     if args.save and ctx.rank == 0:
         steps.save_checkpoint(args.save, model, opt, epoch0 + 1)
     line = {"what": "training step, reference model on the drop-in ops", "model": args.model, "n_gpus": ctx.world_size,
@@ -117,7 +125,9 @@ def run(args, hook=None):
             "grad_allreduce": "DistributedDataParallel (RCCL)" if ctx.world_size > 1 and not cpu else
                               ("DistributedDataParallel (gloo)" if ctx.world_size > 1 else "none (1 rank)"),
             "peak_mem_GB": None if cpu else round(torch.cuda.max_memory_allocated() / 2 ** 30, 3),
-            "loss_first_last": [round(losses[0], 5), round(losses[-1], 5)] if losses else None, "dtype": "f32",
+            "loss_first_last": [round(losses[0], 5), round(losses[-1], 5)] if losses else None,
+            "amp": ("%s, %s (%d sites)" % (args.amp, "cast arm" if args.amp_cast_arm else "16-bit-storage kernels", n_amp)) if amp is not None else False,
+            "dtype": {None: "f32", torch.bfloat16: "bf16 convolutions, f32 guided aggregation", torch.float16: "f16 convolutions, f32 guided aggregation"}[amp],
             "data": "synthetic", "weights": "random init" if not args.resume else args.resume, "kernel_share": share}
     gdist.finish(ctx)
     if ctx.rank == 0:

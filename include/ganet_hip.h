@@ -409,6 +409,44 @@ int ganet_cost_volume_forward_16(const void *x, const void *y, void *cost, int N
 int ganet_l1_normalize_forward_mixed(const void *x, float *y0, float *y1, float *y2, float *y3,
                                      int N, int G, int C, int K, int H, int W, int x_type, void *stream);
 
+/* ABI v14 (additions).  Training under autocast: batch statistics on 16-bit storage and the backwards the inference entries
+ * above left out (ganet_amd/csrc/mixed_train_kernels.h).  fp32 / fp64 arithmetic on the exactly up-cast operands, one rounding
+ * on each 16-bit store.
+ *   bn train     ganet_bn_train_forward / _backward with a 16-bit x: their arithmetic term for term, their two launches each way
+ *                over the same rows (ganet_bn_workspace is reused), no atomics, two runs bit-identical.  Three combinations:
+ *                    x 16-bit, rem NULL, y and grad_y x's format   (every BasicConv)
+ *                    x 16-bit, rem NULL, y and grad_y fp32         (the BasicConv in front of an SGABlock)
+ *                    x 16-bit, rem fp32, y and grad_y x's format   (the SGABlock tail)
+ *                grad_x has x's format, grad_rem is fp32, the statistics, running buffers, grad_weight and grad_bias are fp32.
+ *                y, grad_x and grad_rem must not alias an input (x is saved for the backward: no in-place form).  A NULL output
+ *                is not computed; with neither grad_x nor grad_rem the second launch is one block per channel.
+ *                The statistics are reductions whose lanes cover other elements than the fp32 entry's: they agree with it to
+ *                rounding, and bit for bit where every partial sum is exact; y is the fp32 expression of the RETURNED statistics,
+ *                rounded once.
+ *   cost volume  ganet_cost_volume_backward on fp16 | bf16 grad_cost, grad_x and grad_y (`type` names the one format): fp32 sums
+ *                over the disparity ascending, == convert(ganet_cost_volume_backward(upcast(grad_cost))) bit for bit.
+ *   l1 normalize ganet_l1_normalize_backward with an fp16 | bf16 x, fp32 incoming gradients and a grad_x of x's format:
+ *                == convert(ganet_l1_normalize_backward(upcast(x), ..)) bit for bit.
+ * 16-byte requests where the inner size is a multiple of 8 and the bases are 16-byte aligned, scalar ones otherwise.  NULL,
+ * non-positive sizes, M = N*S = 1, an unknown type code, a forbidden alias: GANET_E_INVALID.  A combination that is not compiled
+ * (an fp32 x, a 16-bit rem, a residual with an fp32 y, two different 16-bit formats in one call): GANET_E_UNSUPPORTED.
+ * Replaces: under torch.autocast, models/GANet_deep.py:35-41 and :270-277 (BatchNorm, `x += rem`, relu behind a 16-bit
+ *           convolution, with their autograd backward and the casts around them), libs/GANet/modules/GANet.py:114-134
+ *           (GetCostVolume's backward) and the backward of models/GANet_deep.py:263-268 / :235 (F.normalize of the guidance
+ *           and of the LGA filters). */
+int ganet_bn_train_forward_mixed(const void *x, const float *rem, const float *weight, const float *bias,
+                                 float *running_mean, float *running_var, double *workspace, void *y,
+                                 float *save_mean, float *save_invstd, int N, int C, int S, int momentum_bits, int eps_bits,
+                                 int relu, int x_type, int rem_type, int y_type, void *stream);
+int ganet_bn_train_backward_mixed(const void *x, const float *rem, const void *grad_y, const float *weight, const float *bias,
+                                  const float *save_mean, const float *save_invstd, double *workspace,
+                                  void *grad_x, float *grad_rem, float *grad_weight, float *grad_bias,
+                                  int N, int C, int S, int relu, int x_type, int rem_type, int gy_type, void *stream);
+int ganet_cost_volume_backward_16(const void *grad_cost, void *grad_x, void *grad_y, int N, int C, int Dn, int H, int W,
+                                  int type, void *stream);
+int ganet_l1_normalize_backward_mixed(const void *x, const float *gy0, const float *gy1, const float *gy2, const float *gy3,
+                                      void *grad_x, int N, int G, int C, int K, int H, int W, int x_type, void *stream);
+
 /* ---------------------------------------------------------------- image I/O ------ */
 
 /* ABI v14.  The two ends around the model: a stereo pair of uint8 images becomes the model's standardised fp32 input, the
