@@ -35,7 +35,16 @@ the call's own y, and hold the forward's zero set only outside the bar; BnRelu h
 arg-max is the oracle's, held by equality, and float64 is evaluated on those selections; the losses' thresholds act on
 fl32(p - t), one defined rounding of exact inputs that both sides perform alike; Softmin, the regressions, the cost volume
 and the convolution are smooth or linear; trilinear interpolation is continuous across its cell boundaries (the weight of the
-cell that changes is 0 there), and its reference is ATen's own fp32 index arithmetic."""
+cell that changes is 0 there), and its reference is ATen's own fp32 index arithmetic.
+
+Mixed precision.  A step under torch.autocast (`run_model(amp=, scaler=, mixed=)`: harness.steps.predict / train_step themselves) is
+recorded the same way: the Functions of ganet_amd.functions.mixed_train and the launch functions of ganet_amd.functions.mixed are
+wrapped, a 16-bit tensor is kept as its bit patterns with a format tag (`Half`; `up` is the exact up-cast; no ATen cast stands in
+the recorder), and each 16-bit form is held to the float64 statement of the CORRESPONDING fp32 op on the up-cast inputs, a 16-bit
+output getting half an ulp of its format on top of the fp32 kind's bar (the section in front of CHECKERS).  The fp32 kinds
+inside such a step -- on rounded activations and, under a GradScaler, on gradients that carry its scale -- go through the
+checkers they have.  tests/test_gpu_mixed_calls.py runs it on the device, tests/mixed_call_cases.py is the numpy model the
+checkers are calibrated on."""
 import collections
 import contextlib
 import inspect
@@ -57,6 +66,8 @@ import loss_cases
 import loss_ref64
 import misc_cases as mc
 import misc_ref64 as m64
+import mixed_cases as mxc
+import mixed_train_cases as mtc
 import sga_ref64_cases as sc
 import value_cases as vc
 
@@ -81,8 +92,41 @@ class Record:
         return f"{self.kind}{shapes}"
 
 
+class Half(np.ndarray):
+    """a 16-bit tensor as the recorder keeps it: its bit patterns (uint16) with the format tag `fmt` (mixed_cases.F16 / BF16).
+    numpy has no bfloat16 and an ATen cast would be an operation of the product standing inside its own check, so the bits
+    travel as they are; `up(a)` is mixed_cases' exact up-cast.  Views, copies and zeros_like keep the tag."""
+
+    def __new__(cls, bits, fmt):
+        a = np.asarray(bits, np.uint16).view(cls)
+        a.fmt = fmt
+        return a
+
+    def __array_finalize__(self, obj):
+        self.fmt = getattr(obj, "fmt", None)
+
+
+_TORCH_FMT = {torch.float32: mxc.F32, torch.float16: mxc.F16, torch.bfloat16: mxc.BF16}
+
+
+def fmt_of(a):
+    return a.fmt if isinstance(a, Half) else mxc.F32
+
+
+def up(a):
+    """the float32 values of a recorded array: exact for a Half, the array itself otherwise (None stays None)"""
+    return mxc.up(np.asarray(a), a.fmt).reshape(a.shape) if isinstance(a, Half) else a
+
+
+def _bits(t):
+    t = t.detach().cpu()
+    if t.dtype in (torch.float16, torch.bfloat16):
+        return Half(t.contiguous().view(torch.int16).numpy().view(np.uint16), _TORCH_FMT[t.dtype])
+    return t.numpy()
+
+
 def _host(t):
-    return t.detach().cpu().numpy().copy() if isinstance(t, torch.Tensor) else t
+    return _bits(t).copy() if isinstance(t, torch.Tensor) else t
 
 
 def _seq(v):
@@ -90,8 +134,9 @@ def _seq(v):
 
 
 def _same(t, before):
-    now = t.detach().cpu().numpy()
-    return now.shape == before.shape and now.dtype == before.dtype and now.tobytes() == before.tobytes()      # bits: a NaN is itself
+    now = _bits(t)
+    return now.shape == before.shape and now.dtype == before.dtype and fmt_of(now) == fmt_of(before) \
+        and now.tobytes() == before.tobytes()                                                               # bits: a NaN is itself
 
 
 def _changed(tensors, before, phase, prefix, record):
@@ -128,6 +173,8 @@ def _wrap_function(patch, records, cls):
             r.saved = {"tmp": _host(tmp), "mask": _host(mask)}
         elif kind == "LgaRegressFunction":             # the pass's own volume and norm: the call's signs (check_lga_regress)
             r.saved = {"y": _host(ctx.saved_tensors[2]), "snorm": _host(ctx.saved_tensors[4])}
+        elif kind == "MixedBnReluFunction":            # the call's own statistics: y is held to THEIR fp32 expression, bit for bit
+            r.saved = {"mean": _host(ctx.saved_tensors[4]), "invstd": _host(ctx.saved_tensors[5])}
         # (between forward and backward other ops may legitimately write an input -- BatchNorm's running statistics on the
         # next call of a shared module -- so the backward is compared with what it found, not with the forward's clones)
         before = [_host(t) for t in r.live]
@@ -176,31 +223,64 @@ def recording(monkeypatch, functions, plain=()):
 
 def product_functions():
     """everything in ganet_amd.functions.GANet.__all__, every Function of ganet_amd.functions.fused, and the plain functions
-    that launch a kernel without one: the two inference forms of SGA and the image front and back end"""
+    that launch a kernel without one: the two inference forms of SGA and the image front and back end; the mixed-precision
+    forms: every Function of ganet_amd.functions.mixed_train and the five launch functions of ganet_amd.functions.mixed (owners:
+    every module that binds the name -- harness.fuse and harness.steps reach `cast` and the normalisations through the module)"""
     import ganet_amd.functions.fused as ff
     import ganet_amd.functions.GANet as fg
+    import ganet_amd.functions.mixed as fm
+    import ganet_amd.functions.mixed_train as ft
     import ganet_amd.modules.fused as mf
+    import ganet_amd.modules.mixed as mm
+    from harness import fuse
     fns = [getattr(fg, n) for n in fg.__all__]
     fns += [v for v in vars(ff).values() if isinstance(v, type) and issubclass(v, torch.autograd.Function) and v.__module__ == ff.__name__]
-    return fns, [((fg, ff), "_sga_infer"), ((ff, mf), "sga_forward_infer"), ((ff, mf), "stereo_input"), ((ff, mf), "window_f32"),
-                 ((ff, mf), "disparity_to_u16")]
+    fns += [getattr(ft, n) for n in ft.__all__]
+    # (harness.fuse binds sga_forward_infer by name for the mixed-precision inference forward: without it among the owners the
+    # four calls of such a pass go unrecorded -- found by the binder census of tests/test_model_calls_cpu.py)
+    return fns, [((fg, ff), "_sga_infer"), ((ff, mf, fuse), "sga_forward_infer"), ((ff, mf), "stereo_input"), ((ff, mf), "window_f32"),
+                 ((ff, mf), "disparity_to_u16"), ((fm,), "cast"), ((fm, mm), "bn_apply_mixed"), ((fm, mm), "cost_volume_16"),
+                 ((fm,), "normalize_guidance_mixed"), ((fm,), "normalize_filters_mixed")]
+
+
+MIXED_PLAIN = ("cast", "bn_apply_mixed", "cost_volume_16", "normalize_guidance_mixed", "normalize_filters_mixed")
 
 
 REBINDERS = ("use_fused_ops", "use_fused_bn", "use_fused_disp_tail", "use_fused_disp_conv")
 
 
-def run_model(monkeypatch, model, batch, max_disp, rebinders=(), name="GANet_deep", fused_loss=None):
+def run_model(monkeypatch, model, batch, max_disp, rebinders=(), name="GANet_deep", fused_loss=None, amp=None, scaler=None, mixed=None,
+              kernels=True):
     """A ready model (already on its device) under the recorder: `rebinders` -- names of harness.fuse's functions out of REBINDERS
     -- applied in the order given (each must find a site), then steps.predict under no_grad, then one training step:
     steps.loss_mix on the stock call forms, the fused DisparityLoss on the fused ones (fused_loss: default, whether anything
-    was rebound).  batch = (left, right, target).  -> (records of predict, records of the training step)"""
+    was rebound).  batch = (left, right, target).  -> (records of predict, records of the training step)
+
+    amp = torch.bfloat16 | torch.float16 with mixed = "infer" | "train": after the rebinders, harness.fuse.use_mixed_precision resp.
+    use_mixed_precision_training(model, amp, kernels=kernels), then the harness's OWN step under the recorder --
+    steps.predict(model, left, right, amp=amp) resp. steps.train_step(..., amp=amp, scaler=scaler) with SGD at lr = 0 and the
+    fused DisparityLoss -- so that its autocast region, its cast of the images and scaler.scale / step / update are what runs.
+    A model prepared for one of the two runs that one alone: -> (records of predict, []) resp. ([], records of the step)."""
     from ganet_amd.modules.fused import DisparityLoss
     from harness import fuse, steps
     for rb in rebinders:
         assert rb in REBINDERS, rb
         assert getattr(fuse, rb)(model) > 0, rb
-    fused_loss = bool(rebinders) if fused_loss is None else fused_loss
     left, right, target = batch
+    if amp is not None:
+        assert mixed in ("infer", "train"), mixed
+        prepare = fuse.use_mixed_precision if mixed == "infer" else fuse.use_mixed_precision_training
+        assert prepare(model, amp, kernels=kernels) > 0
+        with recording(monkeypatch, *product_functions()) as records:
+            if mixed == "infer":
+                steps.predict(model, left, right, amp=amp)
+                return records, []
+            loss, _ = steps.train_step(model, torch.optim.SGD(model.parameters(), lr=0.0), name, left, right, target, max_disp,
+                                       steps.criterion(True), fused_loss=DisparityLoss.for_model(name, max_disp), amp=amp, scaler=scaler)
+            assert loss is not None and bool(torch.isfinite(loss)), loss
+        return [], records
+    assert scaler is None and mixed is None, "a GradScaler and the mixed-precision sites belong to a step under autocast: give amp"
+    fused_loss = bool(rebinders) if fused_loss is None else fused_loss
     with recording(monkeypatch, *product_functions()) as records:
         steps.predict(model, left, right)
         n_infer = len(records)
@@ -239,6 +319,9 @@ DECLARED = {
     "_sga_infer": lambda r: {"arg5"},                                          # `output`
     "DisparityLossFunction": lambda r: {"arg2"},                               # the fp64 workspace
     "stereo_input": lambda r: {"arg6", "arg7"},                                # out_left / out_right, where given
+    "MixedBnReluFunction": lambda r: {"arg4", "arg5"},                         # running_mean / running_var, as BnReluFunction
+    "bn_apply_mixed": lambda r: {"arg0"} if r.args[6] else set(),              # inplace: y overwrites x
+    # the other mixed-precision forms (cost volume, both normalisations, the casts) declare nothing written: no entry
     # UpSoftminRegressionFunction and DispConvFunction declare nothing written ("neither is written"; their workspaces are
     # their own): no entry, any write is reported
 }
@@ -635,11 +718,13 @@ def _relu_adjoint(r, y, scale, i_t, i_rem):
     return q
 
 
-def _affine_relu(name, got, t, rem, scale, shift, relu=True):
+def _affine_relu(name, got, t, rem, scale, shift, relu=True, fmt=mxc.F32):
     """y = relu(scale[c] t + shift[c] + rem) in at most three fp32 roundings (product, two additions; an fma build has two),
     each at most u times a partial result that |scale t| + |shift| + |rem| bounds: the case tables' EQUAL on dyadic inputs
     becomes 3 u (|scale t| + |shift| + |rem|) on real ones, one rounding where there is nothing but t + rem.  The ReLU is
-    1-Lipschitz: the bar holds through it, and where float64 is above / below the bar the sign is decided."""
+    1-Lipschitz: the bar holds through it, and where float64 is above / below the bar the sign is decided.
+    fmt: the format y was stored in (`got`: its up-cast) -- a 16-bit store adds its one rounding, half an ulp of fmt at
+    |s| + bar, to the bar and to the band in which the zero set is not decided; fp32 (the default): nothing is added."""
     C = t.shape[1]
     b = lambda v: v.astype(np.float64).reshape((1, C) + (1,) * (t.ndim - 2))      # noqa: E731
     t64 = t.astype(np.float64)
@@ -649,6 +734,8 @@ def _affine_relu(name, got, t, rem, scale, shift, relu=True):
     else:
         s = b(scale) * t64 + b(shift) + rem64
         bar = 3 * ONE_ROUNDING * (np.abs(b(scale) * t64) + np.abs(b(shift)) + np.abs(rem64))
+    if fmt != mxc.F32:
+        bar = bar + mtc.half_ulp(np.abs(np.maximum(s, 0.0) if relu else s) + bar, fmt)     # (of the value that is stored)
     if relu:
         assert not (got[s < -bar] != 0).any() and not (got[s > bar] <= 0).any(), (name, "zero set")
     return _within(name, got, np.maximum(s, 0.0) if relu else s, bar)
@@ -826,7 +913,202 @@ def check_disparity_to_u16(r, oracle=None):
     return {"u16": _same_bits("u16", r.outputs[0], io_ref64.disparity_u16(disp, int(hw[0]), int(hw[1]), int(oy), int(ox), scale))}
 
 
+# ---- the mixed-precision forms: 16-bit storage around fp32 arithmetic (ganet_amd.functions.mixed / mixed_train) --------------------------
+# A 16-bit value's up-cast is exact, so every checker below evaluates the float64 statement of the CORRESPONDING fp32 op on the
+# up-cast recorded inputs -- the statements above, no other -- and holds each output by its storage: an fp32 output to the fp32
+# kind's bar, restated relative to the recorded data as above; a 16-bit output to that bar plus half an ulp of its format at
+# |want| + bar (mixed_train_cases.half_ulp), the one rounding the store adds.  There is no new tolerance constant.  Gradients are
+# compared at the magnitude they were recorded at: under a GradScaler they carry its scale, a power of two, and every adjoint
+# below is linear in its incoming gradient -- statement and bar scale with it exactly, short of the format's range, which
+# `_within` (not finite) and check_cast (a finite value that left the range) report.
+def _held(name, got, want, bar):
+    want = np.asarray(want, np.float64)
+    if isinstance(got, Half):
+        bar = bar + mtc.half_ulp(np.abs(want) + bar, got.fmt)
+    return _within(name, up(got), want, bar)
+
+
+def _cast_bits(name, got, src, dst):
+    """got: bits equal to mixed_cases.convert (round to nearest even) of `src` to the format dst; the same format: a copy"""
+    assert fmt_of(got) == dst and got.shape == src.shape, (name, fmt_of(got), dst, got.shape, src.shape)
+    want = mxc.cast_expected(np.asarray(src), fmt_of(src), dst)
+    if fmt_of(src) == dst:
+        assert np.asarray(got).tobytes() == want.tobytes(), (name, "a cast to the same type changed a pattern")
+    else:
+        mxc.assert_same(np.ascontiguousarray(np.asarray(got)).ravel(), want, dst, name)
+        s = np.asarray(up(src)).ravel()
+        lost = np.isfinite(s) & ~np.isfinite(mxc.up(want, dst) if dst != mxc.F32 else want)
+        assert not lost.any(), (name, f"{int(lost.sum())} finite values left the range of {mxc.FMT_NAME[dst]}, the largest {np.abs(s[lost]).max():.3g}")
+    return 0.0
+
+
+def check_cast(r, oracle=None):
+    """CastFunction / cast: a conversion has no bar.  Forward: the recorded input converted to the asked type; backward: the
+    incoming gradient converted to the input's type"""
+    t, dtype = r.args[:2]
+    q = {"y": _cast_bits(f"{r!r} y", r.outputs[0], t, _TORCH_FMT[dtype])}
+    if r.grad_in is not None:
+        q["g"] = _cast_bits(f"{r!r} g", r.grad_in[0], r.grad_out[0], fmt_of(t))
+    return q
+
+
+def check_cost_volume_16(r, oracle=None):
+    """forward: a copy with a mask -- misc_ref64.cost_volume on the recorded BIT PATTERNS (integers below 2^16, exact in float64;
+    the mask's zero is the pattern 0).  backward: check_cost_volume's, fp32 sums over at most Dn planes of the up-cast gradient
+    (gamma_Dn sum |terms|), stored in the gradient's format"""
+    x, y, Dn = r.args[:3]
+    cost = r.outputs[0]
+    assert isinstance(x, Half) and fmt_of(y) == x.fmt and fmt_of(cost) == x.fmt, (repr(r), fmt_of(x), fmt_of(y), fmt_of(cost))
+    want = m64.cost_volume(np.asarray(x), np.asarray(y), Dn)
+    assert cost.shape == want.shape and np.array_equal(np.asarray(cost), want.astype(np.uint16)), (repr(r), "cost: not the copy")
+    q = {"cost": 0.0}
+    if r.grad_in is not None:
+        assert all(fmt_of(g) == fmt_of(r.grad_out[0]) for g in r.grad_in[:2]), repr(r)
+        g, C = up(r.grad_out[0]), x.shape[1]
+        want, mag = m64.cost_volume_adjoint(g, C), m64.cost_volume_adjoint(np.abs(g), C)
+        for k, i in (("gx", 0), ("gy", 1)):
+            q[k] = _held(k, r.grad_in[i], want[i], _gamma(Dn) * mag[i])
+    return q
+
+
+def _l1_dims(r):
+    x = r.args[0]
+    if r.kind in ("NormalizeGuidanceMixedFunction", "normalize_guidance_mixed"):
+        return x, 4, int(r.args[1]), 5
+    return x, 1, 1, x.shape[1]
+
+
+def check_l1_mixed(r, oracle=None):
+    """both normalisations, Function and inference form: check_l1_normalize's statement and bars on the up-cast x (sign, zero set
+    and clamp act on the recorded input); the outputs are fp32; gx is stored in x's format"""
+    x16, G, C, K = _l1_dims(r)
+    assert isinstance(x16, Half), (repr(r), "a 16-bit input was expected")
+    x = up(x16)
+    N, _, H, W = x.shape
+    x6 = x.reshape(N, G, C, K, H, W)
+    want, clamped = m64.l1_normalize(x6, 3), m64.l1_clamped(x6, 3)
+    assert len(r.outputs) == G and all(not isinstance(o, Half) and o.dtype == np.float32 for o in r.outputs), repr(r)
+    q = {}
+    for g in range(G):
+        y = r.outputs[g].reshape(N, C, K, H, W)
+        q[f"y{g}"] = _close(f"y{g}", y, want[:, g], 1e-5, 1e-6, rel_only=clamped[:, g])
+        mc.check([mc.Cmp(f"y{g} zero set", y, x6[:, g] == 0, "zeros")])
+    if r.grad_in is not None:
+        gys = np.stack([np.zeros((N, C, K, H, W), np.float32) if r.grad_out[g] is None else r.grad_out[g].reshape(N, C, K, H, W) for g in range(G)], 1)
+        wgx = m64.l1_normalize_adjoint(x6, gys, 3)
+        gx = r.grad_in[0]
+        assert fmt_of(gx) == x16.fmt, (repr(r), "the gradient of x has x's format")
+        a = _atol(1e-5, wgx, ~clamped if clamped.any() else None)                # `_close`, as check_l1_normalize calls it
+        q["gx"] = _held("gx", gx.reshape(x6.shape), wgx, np.where(clamped, 0.0, a) + 1e-4 * np.abs(wgx))
+    return q
+
+
+def mixed_bn_z32(x, rem, weight, bias, mean, invstd):
+    """bn_kernels.h's fp32 expression behind a 16-bit x, with the statistics the call returned: scale = fl(weight invstd),
+    shift = fma(-mean, scale, bias), z = fma(x, scale, shift), then -- where a residual is added -- z = fl(z + rem): ONE more fp32
+    rounding, before the ReLU and before the store's (bn_z).  x: [N,C,S] float32"""
+    C = x.shape[1]
+    w = np.ones(C, np.float32) if weight is None else weight
+    b = np.zeros(C, np.float32) if bias is None else bias
+    with np.errstate(all="ignore"):
+        scale = (w * invstd).astype(np.float32)
+        shift = mtc.fma32(-mean, scale, b)
+        z = mtc.fma32(x, scale[None, :, None], shift[None, :, None])
+        return z if rem is None else (z + rem).astype(np.float32)
+
+
+def check_mixed_bn_relu(r, oracle=None):
+    """MixedBnReluFunction: check_bn_relu's construction -- a bn_cases.Case around the recorded tensors, x and a 16-bit grad_y
+    up-cast, mean_term=True -- with mixed_train_cases' general tier and tests/test_gpu_mixed_train.py's bars:
+      mean, invstd  the call's own (Record.saved) inside bn_cases' bars; a record with gradients and without them fails
+      y             BITS equal to convert(relu(z32), y's type), z32 = mixed_bn_z32 on those statistics: no bar.  The ReLU's mask,
+                    forward and backward, is z32 > 0 (the backward recomputes the same expression): that is the call's own mask,
+                    handed to bn_ref64.Reference for the elements float64 cannot decide, and it must agree with float64's
+                    everywhere else
+      running_*     bn_cases' bars, on what the call left in the buffers
+      grad_x        bar_grad_x(mean term) + half an ulp of x's format
+      grad_rem      fp32, equal to the masked gradient
+      grad_weight, grad_bias   bn_cases' bars with the mean term"""
+    x16, rem, weight, bias, rmean, rvar, momentum, eps, relu = r.args[:9]
+    out_dtype = r.args[9] if len(r.args) > 9 else None
+    what = repr(r)
+    assert isinstance(x16, Half), (what, "a 16-bit x was expected")
+    y16 = r.outputs[0]
+    assert fmt_of(y16) == (x16.fmt if out_dtype is None else _TORCH_FMT[out_dtype]), (what, "y's type", fmt_of(y16))
+    N, C = x16.shape[:2]
+    shape = (N, C, x16.size // (N * C))
+    x = up(x16).reshape(shape)
+    rem3 = None if rem is None else rem.reshape(shape)
+    grads = r.grad_in is not None
+    c = object.__new__(bn_cases.Case)
+    c.name, c.shape, c.relu, c.offset, c.exact, c.momentum, c.eps = what, shape, bool(relu), 0, False, momentum, eps
+    c.x, c.rem, c.compare_grads, c.mean_term, c.nudged = x, rem3, grads, True, 0
+    if grads:
+        assert fmt_of(r.grad_out[0]) == fmt_of(y16), (what, "grad_y has y's type")
+    c.gy = up(r.grad_out[0]).reshape(shape) if grads else np.zeros(shape, np.float32)
+    c.weight, c.bias, c.running_mean, c.running_var = weight, bias, rmean, rvar
+    q = {}
+    y = up(y16).reshape(shape)
+    if "mean" in r.saved:
+        z32 = mixed_bn_z32(x, rem3, weight, bias, r.saved["mean"], r.saved["invstd"])
+        with np.errstate(invalid="ignore"):
+            positive = z32 > 0
+            y32 = np.where(z32 <= 0, np.float32(0), z32) if relu else z32
+        mxc.assert_same(np.asarray(y16).reshape(shape), mxc.convert(y32, fmt_of(y16)).reshape(shape), fmt_of(y16), f"{what}: y")
+        q["y"] = 0.0
+    else:
+        assert not grads, (what, "a call with gradients must keep its own mean and invstd (Record.saved)")
+        positive = y > 0
+    c._ref = ref = bn_ref64.Reference(*c.inputs(), relu_positive=positive)
+    if relu:
+        wrong = ~ref.undecided() & (positive != (ref.z > 0))
+        assert not wrong.any(), (what, f"the ReLU's mask differs from float64's at {int(wrong.sum())} decided elements")
+    if "mean" in r.saved:
+        q["mean"] = bn_cases.within("save_mean", r.saved["mean"], ref.mean, 2.0 ** -23 * ref.mean_abs_x, False)
+        q["invstd"] = bn_cases.within("save_invstd", r.saved["invstd"], ref.invstd, 2.0 ** -22 * ref.invstd, False)
+    else:
+        q["y"] = _held("y", y16.reshape(shape), ref.y, ref.bar_y())
+    if rmean is not None:
+        m = ref.m
+        q["running_mean"] = bn_cases.within("running_mean", r.after.get(4, rmean), ref.running_mean,
+                                            2.0 ** -22 * ((1 - m) * np.abs(ref.old_mean) + m * np.abs(ref.mean)), False)
+        q["running_var"] = bn_cases.within("running_var", r.after.get(5, rvar), ref.running_var,
+                                           2.0 ** -22 * ((1 - m) * np.abs(ref.old_var) + m * np.abs(ref.new_var)), False)
+    if grads:
+        gx, grem, gw, gb = r.grad_in[:4]
+        if gx is not None:
+            assert fmt_of(gx) == x16.fmt, (what, "grad_x has x's type")
+            q["grad_x"] = _held("grad_x", gx.reshape(shape), ref.grad_x, ref.bar_grad_x(True))
+        if grem is not None:
+            mxc.assert_same(np.ascontiguousarray(grem).reshape(shape), ref.g.astype(np.float32), mxc.F32, f"{what}: grad_rem is not g")
+            q["grad_rem"] = 0.0
+        if gw is not None:
+            bar = 2.0 ** -22 * ref.invstd * ref.sum_abs_gxm + 2.0 ** -22 * np.abs(ref.mean) * ref.invstd * np.abs(ref.sum_g)
+            q["grad_weight"] = bn_cases.within("grad_weight", gw, ref.grad_weight, bar, False)
+        if gb is not None:
+            q["grad_bias"] = bn_cases.within("grad_bias", gb, ref.grad_bias, 2.0 ** -22 * ref.sum_abs_g, False)
+    q["undecided"] = float(ref.undecided().sum())
+    return q
+
+
+def check_bn_apply_mixed(r, oracle=None):
+    """the folded BatchNorm of inference on 16-bit storage: `_affine_relu`'s bound on the up-cast x / rem, plus half an ulp of the
+    format y is stored in"""
+    x, rem, scale, shift, relu, out_dtype, _ = r.args
+    y = r.outputs[0]
+    assert fmt_of(y) == (fmt_of(x) if out_dtype is None else _TORCH_FMT[out_dtype]), (repr(r), "y's type", fmt_of(y))
+    return {"y": _affine_relu("y", up(y), up(x), up(rem), scale, shift, relu, fmt=fmt_of(y))}
+
+
+MIXED_CHECKERS = {
+    "MixedBnReluFunction": check_mixed_bn_relu, "CostVolume16Function": check_cost_volume_16,
+    "NormalizeGuidanceMixedFunction": check_l1_mixed, "NormalizeFiltersMixedFunction": check_l1_mixed, "CastFunction": check_cast,
+    "cast": check_cast, "bn_apply_mixed": check_bn_apply_mixed, "cost_volume_16": check_cost_volume_16,
+    "normalize_guidance_mixed": check_l1_mixed, "normalize_filters_mixed": check_l1_mixed,
+}
+
 CHECKERS = {
+    **MIXED_CHECKERS,
     "SgaFunction": check_sga, "OracleSga": check_sga, "_sga_infer": check_sga_infer, "sga_forward_infer": check_sga_infer,
     "OracleLgaChain": check_lga, **{k: check_lga for k in LGA_PASSES},
     "GetCostVolumeFunction": check_cost_volume, "DisparityRegressionFunction": check_disparity_regression,

@@ -1015,3 +1015,118 @@ def test_the_stand_in_blocks_are_the_reference_blocks(port_oracle):
         assert _rebound(ref) == _rebound(mine), chain
         assert collections.Counter(type(m).__name__ for m in ref.modules() if "forward" in m.__dict__) == \
             collections.Counter(type(m).__name__ for m in mine.modules() if "forward" in m.__dict__)
+
+
+# ---- the mixed-precision kinds: calibration on a numpy model, teeth, completeness ----------------------------------------------------
+def _mixed_records(oracle, fmt):
+    """[(what, Record)] of every kind of model_calls.MIXED_CHECKERS, built by tests/mixed_call_cases.py from what the stand-in's CPU
+    run hands to each site at 48 x 96 (training: with the gradients that reached it; steps.predict: the inference forms)"""
+    import mixed_call_cases as mcc
+    ops, sites = _ops(oracle)
+    tr, inf = ops["train"], ops["infer"]
+    res = []
+    for k, s in enumerate(x for x in sites if x["g_c"] is not None):
+        res += [(f"cast {s['name']}", r) for r in mcc.cast_records(s["c"], s["g_c"], fmt)]
+    res += [("cost volume", r) for r in mcc.cost_volume_records(tr["cv"][0], fmt)]
+    raw = {d["key"]: d["x"] for d in tr["raw"]}
+    for key, sga in zip(("sg1", "sg11", "sg2", "sg3"), tr["sga"]):
+        res += [(f"guidance {key}", r) for r in mcc.l1_records(raw[key], 4, sga["ks"][0].shape[1], 5, sga["gks"], fmt,
+                                                              "NormalizeGuidanceMixedFunction", "normalize_guidance_mixed")]
+    for key, lga in zip(("lg1", "lg2"), tr["lga"]):
+        res += [(f"filters {key}", r) for r in mcc.l1_records(raw[key], 1, 1, 75, [lga["gf"]], fmt,
+                                                              "NormalizeFiltersMixedFunction", "normalize_filters_mixed")]
+    for s, e in zip(tr["bn"], inf["bn"]):
+        res.append((f"BatchNorm {s['name']}", mcc.bn_train_record(s, fmt)))
+        res.append((f"folded BatchNorm {e['name']}", mcc.bn_apply_record(e, fmt)))
+    assert {r.kind for _, r in res} == set(M.MIXED_CHECKERS)
+    sites_seen = {r.site for _, r in res if r.kind == "MixedBnReluFunction"}
+    assert sites_seen == {"conv", "pre-sga", "tail"}, sites_seen
+    return res
+
+
+@pytest.mark.parametrize("fmt", [2, 1], ids=["bf16", "f16"])
+def test_the_numpy_model_stays_inside_the_bars_of_the_mixed_checkers_and_every_mutation_is_rejected(port_oracle, fmt):
+    """calibration and teeth of every kind of model_calls.MIXED_CHECKERS, per format (fp16: gradients at 256 times their size, as
+    under GradScaler(init_scale=256)): each table's statement -- fp32 on the up-cast, converted once -- is accepted with largest
+    error / bar <= 1 (printed; profiles/r21a_mixed_calls.txt keeps the figures), and every mutation of tests/mixed_call_cases.py is
+    REJECTED on every record it applies to."""
+    import mixed_call_cases as mcc
+    import mixed_cases as mxc
+    assert fmt in mcc.FMTS
+    worst, applied = collections.OrderedDict(), collections.Counter()
+    for what, r in _mixed_records(port_oracle, fmt):
+        check = M.CHECKERS[r.kind]
+        q = check(r, port_oracle)
+        for k, v in q.items():
+            worst[r.kind, k] = max(worst.get((r.kind, k), 0.0), v)
+        for name, slot, bad in mcc.mutations(r):
+            applied[r.kind, name] += 1
+            assert _rejected(check, bad, port_oracle), (what, r.kind, name, slot, "passes")
+    print(f"numpy model {mxc.FMT_NAME[fmt]}, stand-in data 48x96: largest error / bar (bar: 1)\n" + M.fmt(worst))
+    print("mutations rejected, per kind:", dict(applied))
+    ratios = {k: v for k, v in worst.items() if k[1] not in COUNTS}
+    assert max(ratios.values()) <= 1.0, {k: v for k, v in ratios.items() if v > 1.0}
+    for kind in ("MixedBnReluFunction", "CostVolume16Function", "NormalizeGuidanceMixedFunction", "NormalizeFiltersMixedFunction", "CastFunction"):
+        assert all(applied[kind, m] for m in ("zeros", "truncated", "twice", "x256")), (kind, dict(applied))
+    assert all(applied[k, "one term"] for k in ("MixedBnReluFunction", "CostVolume16Function", "NormalizeGuidanceMixedFunction",
+                                                "NormalizeFiltersMixedFunction"))
+    assert all(applied[k, "zeros"] for k in M.MIXED_PLAIN) and all(applied[k, m] for k in ("cast", "bn_apply_mixed") for m in ("truncated", "twice"))
+
+
+# a mixed-precision name that no checker applies to, with the reason
+MIXED_NOT_APPLICABLE = {
+    "_l1_groups": "the private launcher behind normalize_guidance_mixed and normalize_filters_mixed, its only callers: both are wrapped and checked",
+    "TYPE_CODE": "a table of dtype codes, not an op",
+}
+
+
+def test_every_mixed_precision_op_is_recorded_and_has_a_checker():
+    """completeness: every name of functions.mixed_train.__all__ and every function of functions/mixed.py that launches a kernel (its
+    source calls into the native library) or is exported is wrapped by product_functions() AND has a checker, or stands in
+    MIXED_NOT_APPLICABLE with its reason"""
+    import inspect
+    import ganet_amd.functions.mixed as fm
+    import ganet_amd.functions.mixed_train as ft
+    fns, plain = M.product_functions()
+    wrapped = {f.__name__ for f in fns} | {name for _, name in plain}
+    launching = {n for n, f in vars(fm).items() if inspect.isfunction(f) and f.__module__ == fm.__name__ and '.call("ganet_' in inspect.getsource(f)}
+    assert {"cast", "bn_apply_mixed", "cost_volume_16", "_l1_groups"} <= launching
+    names = set(ft.__all__) | set(fm.__all__) | launching
+    assert len(ft.__all__) == 5 and set(M.MIXED_PLAIN) <= names
+    for n in sorted(names):
+        if n in MIXED_NOT_APPLICABLE:
+            assert n not in M.CHECKERS and MIXED_NOT_APPLICABLE[n]
+        else:
+            assert n in wrapped and n in M.CHECKERS, (n, "not recorded or not checked")
+    assert set(MIXED_NOT_APPLICABLE) <= names
+    # the owners are EVERY module of the product that binds the name (all of its modules that hold op call sites are loaded first)
+    import importlib
+    for mod in ("ganet_amd.modules.GANet", "ganet_amd.modules.fused", "ganet_amd.modules.mixed", "harness.fuse", "harness.steps", "harness.predict",
+                "harness.infer", "harness.train"):
+        importlib.import_module(mod)
+    for owners, name in plain:
+        orig = getattr(owners[0], name)
+        binders = {m.__name__ for m in sys.modules.values() if getattr(m, "__name__", "").split(".")[0] in ("ganet_amd", "harness")
+                   and m.__dict__.get(name) is orig}
+        assert binders == {o.__name__ for o in owners}, (name, binders)
+
+
+def test_the_recorder_keeps_16_bit_tensors_as_bits():
+    """model_calls._host on fp16 / bf16: the patterns with their tag, the up-cast exact, a changed bit noticed; fp32 and integer
+    tensors as before"""
+    import mixed_cases as mxc
+    f = torch.tensor([1.0, -2.5, 3.1415927, 65504.0, 1e-8, float("nan")])
+    for dt, fmt in ((torch.bfloat16, mxc.BF16), (torch.float16, mxc.F16)):
+        t = f.to(dt)
+        a = M._host(t)
+        assert isinstance(a, M.Half) and a.fmt == fmt and a.dtype == np.uint16 and a.shape == (6,)
+        assert np.array_equal(M.up(a)[:5], t.float().numpy()[:5]) and np.isnan(M.up(a)[5])
+        assert np.array_equal(np.asarray(a)[:5], mxc.convert(f.numpy(), fmt)[:5])                    # (a NaN's payload aside)
+        assert M._same(t, a) and np.zeros_like(a).fmt == fmt and a.reshape(2, 3).fmt == fmt
+        assert not M._same(t.view(torch.float16 if dt == torch.bfloat16 else torch.bfloat16), a)     # the same bits under the other tag
+        t[0] = 1.0078125                                                                             # one ulp of bf16 above 1
+        assert not M._same(t, a)
+    a = M._host(f)
+    assert type(a) is np.ndarray and a.dtype == np.float32 and M.up(a) is a and M._same(f, a)
+    i = torch.arange(4, dtype=torch.int32)
+    assert M._host(i).dtype == np.int32 and M._same(i, M._host(i))
