@@ -88,6 +88,12 @@ _PROTOS = {
     "ganet_selftest_dpp_wave": [_P, _P, _P],
 }
 EXPORTS = sorted(list(_PROTOS) + ["ganet_last_error"])
+# include/ganet_hip_conv16.h: conv32x1 on a 16-bit x.  Bound like _PROTOS; a table of its own, as EXPORTS is include/ganet_hip.h's
+_PROTOS_CONV16 = {
+    "ganet_disp_conv_forward_16": [_P] * 3 + [_I] * 6 + [_P],
+    "ganet_disp_conv_backward_data_16": [_P] * 3 + [_I] * 6 + [_P],
+    "ganet_disp_conv_backward_weight_16": [_P] * 4 + [_I] * 6 + [_P],
+}
 
 
 class GanetError(RuntimeError):
@@ -115,7 +121,7 @@ class CApi:
         self._lib = ctypes.CDLL(path)
         self._lib.ganet_last_error.restype = ctypes.c_char_p
         self._lib.ganet_last_error.argtypes = []
-        for name, args in _PROTOS.items():
+        for name, args in list(_PROTOS.items()) + list(_PROTOS_CONV16.items()):
             try:
                 fn = getattr(self._lib, name)
             except AttributeError:

@@ -9,6 +9,7 @@
 #include "misc_kernels.h"
 #include "disp_tail_kernels.h"
 #include "disp_conv_kernels.h"
+#include "disp_conv16_kernels.h"
 #include "mixed_kernels.h"
 #include "mixed_train_kernels.h"
 #include "sga_kernels.h"
@@ -24,6 +25,7 @@
 #include <mutex>
 
 #include "../../include/ganet_hip.h"
+#include "../../include/ganet_hip_conv16.h"
 
 #include "ga_launch.h"
 
@@ -2191,4 +2193,77 @@ GA_EXPORT int ganet_selftest_dpp(int *scratch_dev, int *host_out, void *stream)
     expect[6] = bk;
     expect[7] = 16 * row + 120;
   });
+}
+
+// ---- conv32x1 on a 16-bit x (include/ganet_hip_conv16.h; disp_conv16_kernels.h) -----------------------------------------------
+namespace {
+bool type16(int t) { return t == GANET_F16 || t == GANET_BF16; }
+}  // namespace
+
+GA_EXPORT int ganet_disp_conv_forward_16(const void *x, const float *weight, float *y, int N, int C, int D, int H, int W,
+                                         int x_type, void *stream)
+{
+  const char *who = "ganet_disp_conv_forward_16";
+  GA_TRY(check_ptrs(who, x, weight, y));
+  DispConvGeom g;
+  dim3 grid;
+  GA_TRY(check_disp_conv(who, N, C, D, H, W, g, grid));
+  if (!type16(x_type)) return fail(GANET_E_INVALID, "%s: type code %d (fp16 or bf16)", who, x_type);
+  if ((const void *)y == x || y == weight) return fail(GANET_E_INVALID, "%s: y must not alias an input", who);
+  const dim3 block(64 * DCV_WAVES);
+  const uint16_t *xp = (const uint16_t *)x;
+  with_st16(x_type, [&](auto t) {
+    using ST = typename decltype(t)::type;
+    with_flags([&](auto v) { GA_LAUNCH((disp_conv16_fwd<ST, decltype(v)::value>), grid, block, (hipStream_t)stream, xp, weight, y, g); },
+               W % 4 == 0 && aligned8(xp) && aligned16(y));
+  });
+  return check_launch("disp conv forward (16-bit x)");
+}
+
+GA_EXPORT int ganet_disp_conv_backward_data_16(const float *grad_y, const float *weight, void *grad_x, int N, int C, int D,
+                                               int H, int W, int gx_type, void *stream)
+{
+  const char *who = "ganet_disp_conv_backward_data_16";
+  GA_TRY(check_ptrs(who, grad_y, weight, grad_x));
+  DispConvGeom g;
+  dim3 grid;
+  GA_TRY(check_disp_conv(who, N, C, D, H, W, g, grid));
+  if (!type16(gx_type)) return fail(GANET_E_INVALID, "%s: type code %d (fp16 or bf16)", who, gx_type);
+  if (grad_x == (const void *)grad_y || grad_x == (const void *)weight) return fail(GANET_E_INVALID, "%s: grad_x must not alias an input", who);
+  const dim3 block(64 * DCV_WAVES);
+  uint16_t *gp = (uint16_t *)grad_x;
+  with_st16(gx_type, [&](auto t) {
+    using ST = typename decltype(t)::type;
+    with_flags([&](auto v) { GA_LAUNCH((disp_conv16_bwd_data<ST, decltype(v)::value>), grid, block, (hipStream_t)stream, grad_y, weight, gp, g); },
+               W % 4 == 0 && aligned8(gp) && aligned16(grad_y));
+  });
+  return check_launch("disp conv backward (data, 16-bit grad_x)");
+}
+
+GA_EXPORT int ganet_disp_conv_backward_weight_16(const void *x, const float *grad_y, float *workspace, float *grad_weight,
+                                                 int N, int C, int D, int H, int W, int x_type, void *stream)
+{
+  const char *who = "ganet_disp_conv_backward_weight_16";
+  GA_TRY(check_ptrs(who, x, grad_y, workspace, grad_weight));
+  DispConvGeom g;
+  dim3 grid;
+  GA_TRY(check_disp_conv(who, N, C, D, H, W, g, grid));
+  if (!type16(x_type)) return fail(GANET_E_INVALID, "%s: type code %d (fp16 or bf16)", who, x_type);
+  if ((const void *)grad_weight == x || grad_weight == grad_y || (const void *)workspace == x || workspace == grad_y || workspace == grad_weight)
+    return fail(GANET_E_INVALID, "%s: workspace and grad_weight must not alias anything", who);
+  const i64 rows = disp_conv_rows(grid);
+  if (rows * 27 * C > 0x7fffffff) return fail(GANET_E_UNSUPPORTED, "%s: the workspace is beyond ganet_disp_conv_workspace's answer", who);
+  const dim3 block(64 * DCV_WAVES);
+  hipStream_t st = (hipStream_t)stream;
+  const uint16_t *xp = (const uint16_t *)x;
+  with_st16(x_type, [&](auto t) {
+    using ST = typename decltype(t)::type;
+    with_flags([&](auto v) { GA_LAUNCH((disp_conv16_bwd_weight_partials<ST, decltype(v)::value>), grid, block, st, xp, grad_y, workspace, g); },
+               W % 4 == 0 && aligned8(xp) && aligned16(grad_y));
+  });
+  GA_TRY(check_launch("disp conv backward (weight partials, 16-bit x)"));
+  const int K = 27 * C;
+  GA_LAUNCH(disp_conv_bwd_weight_sum, dim3((unsigned)((K + DCV_SUM_COLS - 1) / DCV_SUM_COLS)),
+            dim3(DCV_SUM_COLS * DCV_SUM_SLICES), st, (const float *)workspace, grad_weight, K, rows);
+  return check_launch("disp conv backward (weight sum)");
 }

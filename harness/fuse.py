@@ -23,6 +23,10 @@ use_fused_disp_conv (opt-in, composes with all of the above in any order):
 use_mixed_precision (opt-in, inference; applies use_fused_ops and use_fused_bn where they have not been):
   every site between a convolution and a guided-aggregation op on 16-bit storage, for torch.autocast: see the function
 use_mixed_precision_training (opt-in): the same sites bound to forms that carry gradients, for a training step under autocast
+use_mixed_disp_conv (opt-in, alone or in any order with all of the above):
+  conv32x1          models/GANet_deep.py:212, 232  -> MixedDispConv: DispConv that also takes the 16-bit volume torch.autocast hands it
+                                                   (16-bit siblings of the streaming kernels, fp32 out), so the call does not go
+                                                   back to the library's 16-bit convolution; a later use_fused_disp_conv undoes it
 """
 import types
 
@@ -36,6 +40,7 @@ from ganet_amd.functions.GANet import Lga2Function, LgaFunction, SgaFunction
 from ganet_amd.modules.fused import (BnRelu, DispAggTail, DispConv, DispTail, GuidedSGA, GuidedSGABnRelu, ResidualBnRelu, SoftminDisparityRegression,
                                      TrilinearUpsample, folded_bn)
 from ganet_amd.modules.mixed import MixedBnRelu, MixedTrainBnRelu
+from ganet_amd.modules import mixed_conv as mixed_conv_mod
 
 _UP = TrilinearUpsample()
 
@@ -498,6 +503,28 @@ def use_fused_disp_conv(model, directions=("forward", "data", "weight")):
             conv = m.conv32x1
             # (object.__setattr__: the helper stays out of the module tree, state_dict keys do not move)
             object.__setattr__(conv, "_fused_conv", DispConv(conv, directions))
+            conv.forward = types.MethodType(_conv32x1_forward, conv)
+            n += 1
+    return n
+
+
+def use_mixed_disp_conv(model, kernels=True, directions=("forward", "data", "weight")):
+    """conv32x1 of every Disp and DispAgg on MixedDispConv: DispConv for fp32 input, and for the fp16 / bf16 volume that
+    torch.autocast puts in front of it the 16-bit siblings of the same kernels (DispConv16Function: the fp32 weight parameter
+    itself, an fp32 output, a 16-bit data gradient rounded once) instead of the library's 16-bit convolution.  kernels=False binds
+    the 16-bit case to the cast arm, DispConvFunction on x.float(): the same bits through a cast pass.  `directions`: as
+    use_fused_disp_conv's, for both input widths.
+    Rebinds `forward` on the Conv3d instance, as use_fused_disp_conv does: it works alone, and before or after any other rebinder
+    of this file -- the _conv32x1_f32 of use_mixed_precision / use_mixed_precision_training then meets an fp32 tensor and casts
+    nothing.  The helper stays out of the module tree and no state_dict key moves.  The two rebinders of conv32x1 share one slot:
+    whichever runs LAST holds the site, so a later use_fused_disp_conv puts the fp32-only DispConv back (a 16-bit input then goes
+    to the wrapped convolution again).  Returns the number of sites rebound: 3 on GANet_deep."""
+    n = 0
+    for m in model.modules():
+        if type(m).__name__ in ("Disp", "DispAgg") and isinstance(getattr(m, "conv32x1", None), torch.nn.Conv3d):
+            conv = m.conv32x1
+            # (object.__setattr__: the helper stays out of the module tree, state_dict keys do not move)
+            object.__setattr__(conv, "_fused_conv", mixed_conv_mod.MixedDispConv(conv, directions, kernels))
             conv.forward = types.MethodType(_conv32x1_forward, conv)
             n += 1
     return n

@@ -2,7 +2,7 @@
 """BASELINE.json configs[2]: full GANet-deep inference (9 GA layers... 7 SGA + 2 LGA2) on a KITTI-2015-sized pair
 (1248x384, max_disp 192) on one MI355X, the reference's model on this repository's ops.
 
-    python -m harness.infer [--model GANet_deep] [--height 384] [--width 1248] [--max_disp 192] [--fused] [--fused_bn] [--fused_conv32] [--amp bf16|fp16 [--amp_cast_arm]] [--iters 5]
+    python -m harness.infer [--model GANet_deep] [--height 384] [--width 1248] [--max_disp 192] [--fused] [--fused_bn] [--fused_conv32] [--amp bf16|fp16 [--amp_cast_arm] [--amp_conv32]] [--iters 5]
 
 Prints one JSON line: ms per forward pass (median of --iters, HIP events), peak device memory, parameter count.
 Random-init weights and synthetic standardised images (no checkpoint / dataset offline); predict.py:100-114 is the
@@ -39,12 +39,15 @@ def main():
     ap.add_argument("--amp", choices=("bf16", "fp16"), default=None,
                     help="mixed-precision inference: 16-bit convolutions under torch.autocast around the fp32 GA ops (harness.fuse.use_mixed_precision; implies --fused --fused_bn)")
     ap.add_argument("--amp_cast_arm", action="store_true", help="with --amp: the cast arm (fp32 ops between ATen casts) instead of the 16-bit-storage kernels")
+    ap.add_argument("--amp_conv32", action="store_true", help="with --amp: conv32x1 of every Disp / DispAgg on ganet_amd.modules.mixed_conv.MixedDispConv (the HIP kernels on the 16-bit volume; with --amp_cast_arm its cast arm)")
     ap.add_argument("--no_miopen_find", dest="miopen_find", action="store_false",
                     help="MIOpen immediate mode (heuristic solver choice) instead of timing its solvers per shape")
     ap.add_argument("--kernel_share", action="store_true", help="add the per-group device-time table (torch.profiler over 2 extra passes)")
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     args = ap.parse_args()
+    if args.amp_conv32 and args.amp is None:
+        ap.error("--amp_conv32 needs --amp")
     assert torch.cuda.is_available(), "harness.infer needs a GPU"
     from ganet_amd import _native
     assert not _native.lib().is_simulator
@@ -57,6 +60,7 @@ def main():
     n_fused_conv32 = fuse.use_fused_disp_conv(model) if args.fused_conv32 else 0
     amp = {"bf16": torch.bfloat16, "fp16": torch.float16, None: None}[args.amp]
     n_mixed = fuse.use_mixed_precision(model, amp, kernels=not args.amp_cast_arm) if amp is not None else 0
+    n_amp_conv32 = fuse.use_mixed_disp_conv(model, kernels=not args.amp_cast_arm) if args.amp_conv32 else 0
     left, right, _ = steps.synthetic_batch(args.batch, args.height, args.width, args.max_disp, dev)
     for _ in range(args.warmup):
         out = steps.predict(model, left, right, amp)
@@ -86,6 +90,7 @@ def main():
         "peak_mem_GB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 3),
         "miopen_find": bool(args.miopen_find), "params": sum(p.numel() for p in model.parameters()),
         "amp": ("%s, %s (%d call sites)" % (args.amp, "cast arm" if args.amp_cast_arm else "16-bit-storage kernels", n_mixed)) if amp is not None else None,
+        "amp_conv32": "MixedDispConv (%d call sites)" % n_amp_conv32 if args.amp_conv32 else False,
         "dtype": ("%s convolutions under autocast, f32 guided aggregation and tails" % args.amp) if amp is not None else "f32", "weights": "random init",
         "disp_range": [round(float(out.min()), 3), round(float(out.max()), 3)],
         "device": torch.cuda.get_device_name(0), "kernel_share": share}))

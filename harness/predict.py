@@ -41,7 +41,10 @@ def parse_args(argv=None):
     ap.add_argument("--amp", choices=("bf16", "fp16"), default=None,
                     help="mixed-precision inference: 16-bit convolutions under torch.autocast around the fp32 GA ops (harness.fuse.use_mixed_precision)")
     ap.add_argument("--amp_cast_arm", action="store_true", help="with --amp: the cast arm (fp32 ops between ATen casts) instead of the 16-bit-storage kernels")
+    ap.add_argument("--amp_conv32", action="store_true", help="with --amp: conv32x1 of every Disp / DispAgg on ganet_amd.modules.mixed_conv.MixedDispConv (the HIP kernels on the 16-bit volume; with --amp_cast_arm its cast arm)")
     args = ap.parse_args(argv)
+    if args.amp_conv32 and args.amp is None:
+        ap.error("--amp_conv32 needs --amp")
     if args.crop_height <= 0 or args.crop_width <= 0 or args.max_disp <= 0:
         ap.error("--crop_height, --crop_width and --max_disp are positive")
     return args
@@ -138,6 +141,7 @@ def main(argv=None):
     n_fused_bn = fuse.use_fused_bn(model) if args.fused_bn else 0
     amp = {"bf16": torch.bfloat16, "fp16": torch.float16, None: None}[args.amp]
     n_mixed = fuse.use_mixed_precision(model, amp, kernels=not args.amp_cast_arm) if amp is not None else 0
+    n_amp_conv32 = fuse.use_mixed_disp_conv(model, kernels=not args.amp_cast_arm) if getattr(args, "amp_conv32", False) else 0
 
     def clock():
         torch.cuda.synchronize()
@@ -166,6 +170,7 @@ def main(argv=None):
         "ops": "ganet_amd.modules.fused (%d call sites)" % n_fused if args.fused else "drop-in call forms (libs/)",
         "fused_bn": "BnRelu (%d call sites)" % n_fused_bn if args.fused_bn else False,
         "amp": ("%s, %s (%d call sites)" % (args.amp, "cast arm" if args.amp_cast_arm else "16-bit-storage kernels", n_mixed)) if amp is not None else None,
+        "amp_conv32": "MixedDispConv (%d call sites)" % n_amp_conv32 if n_amp_conv32 else False,
         "dtype": ("%s convolutions under autocast, f32 guided aggregation and tails" % args.amp) if amp is not None else "f32",
         "ms_io_front": round(1e3 * (t1 - t0), 3), "ms_model_first_call": round(1e3 * (t2 - t1), 3), "ms_io_back": round(1e3 * (t3 - t2), 3),
         "weights": args.resume or "random init", "disp_u16_range": [int(u16.min()), int(u16.max())],

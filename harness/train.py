@@ -51,6 +51,7 @@ def parse(argv=None):
     ap.add_argument("--amp", default="", choices=["", "bf16", "fp16"],
                     help="run the step under torch.autocast on a model prepared by harness.fuse.use_mixed_precision_training (fp16: with a GradScaler)")
     ap.add_argument("--amp_cast_arm", action="store_true", help="with --amp: bind every mixed-precision site to the cast arm (kernels=False)")
+    ap.add_argument("--amp_conv32", action="store_true", help="with --amp: conv32x1 of every Disp / DispAgg on ganet_amd.modules.mixed_conv.MixedDispConv (the HIP kernels on the 16-bit volume; with --amp_cast_arm its cast arm)")
     ap.add_argument("--kernel_share", action="store_true", help="add the per-group device-time table (torch.profiler over 2 extra steps, rank 0)")
     ap.add_argument("--resume", default="")
     ap.add_argument("--save", default="")
@@ -80,6 +81,10 @@ def run(args, hook=None):
     if amp is not None and cpu:
         raise SystemExit("--amp needs --device cuda")
     n_amp = fuse.use_mixed_precision_training(steps.unwrap(model), amp, kernels=not args.amp_cast_arm) if amp is not None else 0
+    amp_conv32 = bool(getattr(args, "amp_conv32", False))
+    if amp_conv32 and amp is None:
+        raise SystemExit("--amp_conv32 needs --amp")
+    n_amp_conv32 = fuse.use_mixed_disp_conv(steps.unwrap(model), kernels=not args.amp_cast_arm) if amp_conv32 else 0
     scaler = torch.amp.GradScaler("cuda") if amp == torch.float16 else None
     opt = torch.optim.Adam(model.parameters(), lr=args.lr, betas=(0.9, 0.999))
     epoch0 = 0
@@ -127,6 +132,7 @@ def run(args, hook=None):
             "peak_mem_GB": None if cpu else round(torch.cuda.max_memory_allocated() / 2 ** 30, 3),
             "loss_first_last": [round(losses[0], 5), round(losses[-1], 5)] if losses else None,
             "amp": ("%s, %s (%d sites)" % (args.amp, "cast arm" if args.amp_cast_arm else "16-bit-storage kernels", n_amp)) if amp is not None else False,
+            "amp_conv32": "MixedDispConv (%d call sites)" % n_amp_conv32 if amp_conv32 else False,
             "dtype": {None: "f32", torch.bfloat16: "bf16 convolutions, f32 guided aggregation", torch.float16: "f16 convolutions, f32 guided aggregation"}[amp],
             "data": "synthetic", "weights": "random init" if not args.resume else args.resume, "kernel_share": share}
     gdist.finish(ctx)
