@@ -94,6 +94,12 @@ _PROTOS_CONV16 = {
     "ganet_disp_conv_backward_data_16": [_P] * 3 + [_I] * 6 + [_P],
     "ganet_disp_conv_backward_weight_16": [_P] * 4 + [_I] * 6 + [_P],
 }
+# include/ganet_hip_cl.h: the channels-last inference path.  A table of its own again
+_PROTOS_CL = {
+    "ganet_bn_apply_forward_cl": [_P] * 5 + [_I] * 7 + [_P],
+    "ganet_cost_volume_forward_cl": [_P] * 3 + [_I] * 5 + [_P],
+}
+LAYOUT_PLANAR, LAYOUT_CL = 0, 1          # GANET_LAYOUT_PLANAR / GANET_LAYOUT_CL
 
 
 class GanetError(RuntimeError):
@@ -121,7 +127,7 @@ class CApi:
         self._lib = ctypes.CDLL(path)
         self._lib.ganet_last_error.restype = ctypes.c_char_p
         self._lib.ganet_last_error.argtypes = []
-        for name, args in list(_PROTOS.items()) + list(_PROTOS_CONV16.items()):
+        for name, args in list(_PROTOS.items()) + list(_PROTOS_CONV16.items()) + list(_PROTOS_CL.items()):
             try:
                 fn = getattr(self._lib, name)
             except AttributeError:

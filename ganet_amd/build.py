@@ -30,7 +30,7 @@ def build_hip(force=False, extra_flags=(), out=OUT, verbose=False):
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     # every file under csrc/ (sources, headers, textually included kernels): a new include cannot be forgotten here
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".inc"))]
-    deps += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("ganet_hip.h", "ganet_hip_conv16.h")]
+    deps += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("ganet_hip.h", "ganet_hip_conv16.h", "ganet_hip_cl.h")]
     deps.append(os.path.abspath(__file__))
     if not force and not _stale(out, deps):
         return out

@@ -10,6 +10,7 @@
 #include "disp_tail_kernels.h"
 #include "disp_conv_kernels.h"
 #include "disp_conv16_kernels.h"
+#include "cl_kernels.h"
 #include "mixed_kernels.h"
 #include "mixed_train_kernels.h"
 #include "sga_kernels.h"
@@ -26,6 +27,7 @@
 
 #include "../../include/ganet_hip.h"
 #include "../../include/ganet_hip_conv16.h"
+#include "../../include/ganet_hip_cl.h"
 
 #include "ga_launch.h"
 
@@ -2266,4 +2268,77 @@ GA_EXPORT int ganet_disp_conv_backward_weight_16(const void *x, const float *gra
   GA_LAUNCH(disp_conv_bwd_weight_sum, dim3((unsigned)((K + DCV_SUM_COLS - 1) / DCV_SUM_COLS)),
             dim3(DCV_SUM_COLS * DCV_SUM_SLICES), st, (const float *)workspace, grad_weight, K, rows);
   return check_launch("disp conv backward (weight sum)");
+}
+
+// ---- the channels-last inference path (include/ganet_hip_cl.h; cl_kernels.h) ---------------------------------------------------
+namespace {
+bool layout_code(int l) { return l == GANET_LAYOUT_PLANAR || l == GANET_LAYOUT_CL; }
+}  // namespace
+
+GA_EXPORT int ganet_bn_apply_forward_cl(const float *x, const float *rem, const float *scale, const float *shift, float *y, int N,
+                                        int C, int S, int relu, int x_layout, int rem_layout, int y_layout, void *stream)
+{
+  const char *who = "ganet_bn_apply_forward_cl";
+  GA_TRY(check_ptrs(who, x, scale, shift, y));
+  GA_TRY(check_positive(who, N, C, S));
+  if (!layout_code(x_layout) || !layout_code(rem_layout) || !layout_code(y_layout))
+    return fail(GANET_E_INVALID, "%s: layout codes x=%d rem=%d y=%d", who, x_layout, rem_layout, y_layout);
+  const bool xcl = x_layout == GANET_LAYOUT_CL, ycl = y_layout == GANET_LAYOUT_CL;
+  if (y == rem) return fail(GANET_E_INVALID, "%s: y may alias x, not rem", who);
+  if (y == x && xcl != ycl) return fail(GANET_E_INVALID, "%s: y may alias x only where both have one layout", who);
+  if (rem && rem_layout == GANET_LAYOUT_CL) return fail(GANET_E_UNSUPPORTED, "%s: no kernel for a channels-last rem", who);
+  if (!xcl && !ycl) return fail(GANET_E_UNSUPPORTED, "%s: every operand is planar: that is ganet_bn_apply_forward's case", who);
+  if (C > 65535) return fail(GANET_E_UNSUPPORTED, "%s: C = %d is beyond 65535", who, C);
+  hipStream_t st = (hipStream_t)stream;
+  if (xcl && ycl && !rem) {
+    const i64 n = (i64)N * C * S;
+    with_width<4>(C % 4 == 0 && aligned16(x, y), [&](auto v) {
+      constexpr int V = decltype(v)::value;
+      GA_LAUNCH((cl_bn_stream<V>), dim3(clamp_grid(n / V, CL_BLOCK, CL_MAX_BLOCKS)), dim3(CL_BLOCK), st, x, scale, shift, y, n / V, C, relu);
+    });
+    return check_launch("batch norm apply (channels-last)");
+  }
+  ClGeom g;
+  g.N = N; g.C = C; g.S = S;
+  g.nst = ((i64)S + CL_T - 1) / CL_T;
+  g.ncb = (C + CL_CB - 1) / CL_CB;
+  g.ntiles = (i64)N * g.nst * g.ncb;
+  const dim3 grid(clamp_grid(g.ntiles, 1, CL_MAX_BLOCKS)), block(CL_BLOCK);
+  // the staged operand changes layout, the direct one (if any) is read by the lanes that compute: see cl_kernels.h
+  const float *staged = xcl == ycl ? rem : x, *direct = xcl == ycl ? x : rem;
+  const bool src_cl = !ycl;
+  const int mode = !direct ? 0 : src_cl ? 1 : xcl ? 2 : 3;
+  const float *none = nullptr, *yc = y;
+  const bool vc = C % 4 == 0 && aligned16(xcl ? x : none, ycl ? yc : none);
+  const bool vp = S % 4 == 0 && aligned16(xcl ? none : x, rem, ycl ? none : yc);
+  with_flags([&](auto scl, auto c4, auto p4) {
+    with_int<0, 1, 2, 3>(mode, [&](auto m) {
+      constexpr bool SRC_CL = decltype(scl)::value;
+      constexpr int MODE = decltype(m)::value;
+      if constexpr (SRC_CL ? MODE <= 1 : MODE != 1)
+        GA_LAUNCH((cl_bn_transpose<SRC_CL, MODE, decltype(c4)::value ? 4 : 1, decltype(p4)::value ? 4 : 1>), grid, block, st, staged, direct,
+                  scale, shift, y, g, relu);
+    });
+  }, src_cl, vc, vp);
+  return check_launch("batch norm apply (layout change)");
+}
+
+GA_EXPORT int ganet_cost_volume_forward_cl(const float *x, const float *y, float *cost, int N, int C, int Dn, int H, int W,
+                                           void *stream)
+{
+  const char *who = "ganet_cost_volume_forward_cl";
+  GA_TRY(check_ptrs(who, x, y, cost));
+  GA_TRY(check_positive(who, N, C, Dn, H, W));
+  if (cost == x || cost == y) return fail(GANET_E_INVALID, "%s: cost must not alias an input", who);
+  CvClGeom g;
+  g.N = N; g.C = C; g.Dn = Dn; g.H = H; g.W = W;
+  g.nwb = (W + CV_TW - 1) / CV_TW;
+  g.ndb = (Dn + CV_DB - 1) / CV_DB;
+  g.ncb = (C + CV_CB - 1) / CV_CB;
+  g.ntiles = (i64)N * H * g.nwb * g.ndb * g.ncb;
+  const dim3 grid(clamp_grid(g.ntiles, 1, CL_MAX_BLOCKS)), block(CL_BLOCK);
+  with_width<4>(C % 4 == 0 && aligned16(cost), [&](auto v) {
+    GA_LAUNCH((cost_volume_cl<decltype(v)::value>), grid, block, (hipStream_t)stream, x, y, cost, g);
+  });
+  return check_launch("cost volume forward (channels-last)");
 }

@@ -27,6 +27,9 @@ use_mixed_disp_conv (opt-in, alone or in any order with all of the above):
   conv32x1          models/GANet_deep.py:212, 232  -> MixedDispConv: DispConv that also takes the 16-bit volume torch.autocast hands it
                                                    (16-bit siblings of the streaming kernels, fp32 out), so the call does not go
                                                    back to the library's 16-bit convolution; a later use_fused_disp_conv undoes it
+use_channels_last (opt-in, inference, fp32; applies use_fused_ops and use_fused_bn where they have not been):
+  the cost aggregation on channels_last_3d tensors: the cost volume, every BatchNorm site between two 3-D convolutions and the
+  layout changes around the planar SGA in ClBnRelu's one pass each: see the function
 """
 import types
 
@@ -39,6 +42,7 @@ from ganet_amd.functions.fused import (LgaRegressFunction, SoftminFunction, norm
 from ganet_amd.functions.GANet import Lga2Function, LgaFunction, SgaFunction
 from ganet_amd.modules.fused import (BnRelu, DispAggTail, DispConv, DispTail, GuidedSGA, GuidedSGABnRelu, ResidualBnRelu, SoftminDisparityRegression,
                                      TrilinearUpsample, folded_bn)
+from ganet_amd.modules.channels_last import ClBnRelu, ClGetCostVolume
 from ganet_amd.modules.mixed import MixedBnRelu, MixedTrainBnRelu
 from ganet_amd.modules import mixed_conv as mixed_conv_mod
 
@@ -526,5 +530,101 @@ def use_mixed_disp_conv(model, kernels=True, directions=("forward", "data", "wei
             # (object.__setattr__: the helper stays out of the module tree, state_dict keys do not move)
             object.__setattr__(conv, "_fused_conv", mixed_conv_mod.MixedDispConv(conv, directions, kernels))
             conv.forward = types.MethodType(_conv32x1_forward, conv)
+            n += 1
+    return n
+
+
+# ---- channels-last: the cost aggregation on [N,D,H,W,C] memory (inference, fp32) ---------------------------------------------------
+
+def _cl_inference_only(m):
+    if m.training or torch.is_grad_enabled():
+        raise RuntimeError(f"use_channels_last is inference-only: {type(m).__name__} was called in training mode or with autograd on "
+                           "(model.eval() under torch.no_grad(), as harness.steps.predict does)")
+
+
+def _cl_basicconv_forward(self, x):
+    _cl_inference_only(self)
+    return self._cl_bn(self.conv(x))          # bn + relu in the layout the consumer reads
+
+
+def _cl_sgablock_forward(self, x, g):
+    _cl_inference_only(self)
+    rem = x                                   # planar: the producer's ClBnRelu wrote it so
+    ks = normalize_guidance(g, x.shape[1])
+    x = sga_forward_infer(x.contiguous(), *ks)        # SGA alone: planar in and out, its kernels untouched
+    if self.refine:
+        x = self._cl_bnrelu(x)                # bn_relu, the merge kernel's expression, on the way to channels-last
+        x = self.conv_refine.conv(x)
+    return self._cl_tail(x, rem)              # BatchNorm + rem + ReLU
+
+
+def _cl_cv_forward(self, x, y):
+    return self._cl_cv(x, y)
+
+
+def cl_final_sga(agg):
+    """the SGABlock of a CostAggregation whose output the (planar) disparity tail reads: of the full-resolution blocks sga1,
+    sga2, ... (one digit; sga11 ... sit a level down) the last -- sga3 in GANet_deep, sga2 in GANet11"""
+    blocks = sorted(name for name, m in agg.named_children() if type(m).__name__ == "SGABlock" and len(name) == 4 and name[3].isdigit())
+    return blocks[-1] if blocks else None
+
+
+def use_channels_last(model):
+    """Prepares GANet_deep / GANet11 for fp32 inference with the cost aggregation on channels_last_3d tensors -- the layout
+    MIOpen's 3-D solvers compute in, so that the library has nothing to repack around a convolution.  Applies use_fused_ops and
+    use_fused_bn first where the model has not been rebound; helpers stay out of the module tree (no state_dict key moves).
+    Rebinds, in `cost_agg` only:
+      GANet.cv             ClGetCostVolume: the same values, written [N,D,H,W,2C]
+      BasicConv (3-D, use_bn)   ClBnRelu behind the convolution, whatever layout the convolution answered in (read from strides):
+                           planar out for the producers of an SGABlock's input (_SGA_PRODUCER), channels-last out otherwise
+      SGABlock             sga_forward_infer WITHOUT its BatchNorm epilogue (planar); that BatchNorm + ReLU is ClBnRelu's
+                           planar -> channels-last form (the same expression, the same bits); conv_refine.conv; the tail
+                           ClBnRelu(t, rem planar) -> channels-last -- planar for the last block, whose consumer (conv32x1 /
+                           DispConv) is planar
+      Conv3d / ConvTranspose3d weights of cost_agg   converted once to channels_last_3d (values and state_dict keys unchanged)
+    Conv2x's torch.cat needs nothing: both operands are channels-last by construction.  Every site gives the bits of the planar
+    site it replaces; the convolutions' solvers may differ between layouts.  Refuses a model in training mode and one bound by
+    use_mixed_precision*: 16-bit storage and channels-last do not compose yet.  harness.miopen_env.suggest_channels_last() asks
+    PyTorch to hand MIOpen the tensors as they are; call it before the first convolution of the process.
+    Returns the number of sites."""
+    if model.training:
+        raise RuntimeError("use_channels_last is inference-only: call model.eval() first")
+    mods = list(model.modules())
+    if any("_mixed" in m.__dict__ or "_mixed_bn" in m.__dict__ for m in mods):
+        raise RuntimeError("use_channels_last: the model is bound by use_mixed_precision*; channels-last with 16-bit storage is out of scope")
+    if not any("_fused_sga" in m.__dict__ for m in mods if type(m).__name__ == "SGABlock"):
+        use_fused_ops(model)
+    if not any("_fused_bn" in m.__dict__ for m in mods if type(m).__name__ == "BasicConv"):
+        use_fused_bn(model)
+    aggs = [m for m in mods if type(m).__name__ == "CostAggregation"]
+    planar_out, n = set(), 0
+    for agg in aggs:
+        for sga, producer in _SGA_PRODUCER.items():
+            p = getattr(agg, producer, None)
+            if hasattr(agg, sga) and p is not None:
+                planar_out.add(id(p.conv2 if type(p).__name__ == "Conv2x" else p))
+        final = cl_final_sga(agg)
+        tails = {id(m.conv32x1) for m in agg.modules() if type(m).__name__ in ("Disp", "DispAgg") and hasattr(m, "conv32x1")}     # planar consumers
+        for m in agg.modules():
+            kind = type(m).__name__
+            # (object.__setattr__: the helpers stay out of the module tree, state_dict keys do not move)
+            if kind == "BasicConv" and m.use_bn and isinstance(m.bn, torch.nn.BatchNorm3d):
+                fmt = torch.contiguous_format if id(m) in planar_out else torch.channels_last_3d
+                object.__setattr__(m, "_cl_bn", ClBnRelu(m.bn, relu=bool(m.relu), out_format=fmt))
+                m.forward = types.MethodType(_cl_basicconv_forward, m)
+                n += 1
+            elif kind == "SGABlock":
+                fmt = torch.contiguous_format if final is not None and m is getattr(agg, final) else torch.channels_last_3d
+                if m.refine:
+                    object.__setattr__(m, "_cl_bnrelu", ClBnRelu(m.bn_relu[0], relu=True, out_format=torch.channels_last_3d, inplace=False))
+                object.__setattr__(m, "_cl_tail", ClBnRelu(m.conv_refine.bn if m.refine else m.bn, relu=True, out_format=fmt))
+                m.forward = types.MethodType(_cl_sgablock_forward, m)
+                n += 1
+            elif isinstance(m, (torch.nn.Conv3d, torch.nn.ConvTranspose3d)) and id(m) not in tails:
+                m.weight.data = m.weight.data.contiguous(memory_format=torch.channels_last_3d)     # the same values, the same Parameter
+    for m in mods:
+        if type(m).__name__ == "GetCostVolume" and aggs:
+            object.__setattr__(m, "_cl_cv", ClGetCostVolume(m.maxdisp - 1))        # (the module holds maxdisp + 1)
+            m.forward = types.MethodType(_cl_cv_forward, m)
             n += 1
     return n

@@ -2,7 +2,7 @@
 """BASELINE.json configs[2]: full GANet-deep inference (9 GA layers... 7 SGA + 2 LGA2) on a KITTI-2015-sized pair
 (1248x384, max_disp 192) on one MI355X, the reference's model on this repository's ops.
 
-    python -m harness.infer [--model GANet_deep] [--height 384] [--width 1248] [--max_disp 192] [--fused] [--fused_bn] [--fused_conv32] [--amp bf16|fp16 [--amp_cast_arm] [--amp_conv32]] [--iters 5]
+    python -m harness.infer [--model GANet_deep] [--height 384] [--width 1248] [--max_disp 192] [--fused] [--fused_bn] [--fused_conv32] [--amp bf16|fp16 [--amp_cast_arm] [--amp_conv32]] [--channels_last] [--iters 5]
 
 Prints one JSON line: ms per forward pass (median of --iters, HIP events), peak device memory, parameter count.
 Random-init weights and synthetic standardised images (no checkpoint / dataset offline); predict.py:100-114 is the
@@ -40,6 +40,8 @@ def main():
                     help="mixed-precision inference: 16-bit convolutions under torch.autocast around the fp32 GA ops (harness.fuse.use_mixed_precision; implies --fused --fused_bn)")
     ap.add_argument("--amp_cast_arm", action="store_true", help="with --amp: the cast arm (fp32 ops between ATen casts) instead of the 16-bit-storage kernels")
     ap.add_argument("--amp_conv32", action="store_true", help="with --amp: conv32x1 of every Disp / DispAgg on ganet_amd.modules.mixed_conv.MixedDispConv (the HIP kernels on the 16-bit volume; with --amp_cast_arm its cast arm)")
+    ap.add_argument("--channels_last", action="store_true",
+                    help="the cost aggregation on channels_last_3d tensors (harness.fuse.use_channels_last; fp32 inference, implies --fused --fused_bn)")
     ap.add_argument("--no_miopen_find", dest="miopen_find", action="store_false",
                     help="MIOpen immediate mode (heuristic solver choice) instead of timing its solvers per shape")
     ap.add_argument("--kernel_share", action="store_true", help="add the per-group device-time table (torch.profiler over 2 extra passes)")
@@ -48,6 +50,11 @@ def main():
     args = ap.parse_args()
     if args.amp_conv32 and args.amp is None:
         ap.error("--amp_conv32 needs --amp")
+    if args.channels_last:
+        if args.amp is not None:
+            ap.error("--channels_last is fp32 only: it does not compose with --amp")
+        from harness.miopen_env import suggest_channels_last
+        suggest_channels_last()        # before torch's first convolution
     assert torch.cuda.is_available(), "harness.infer needs a GPU"
     from ganet_amd import _native
     assert not _native.lib().is_simulator
@@ -61,6 +68,7 @@ def main():
     amp = {"bf16": torch.bfloat16, "fp16": torch.float16, None: None}[args.amp]
     n_mixed = fuse.use_mixed_precision(model, amp, kernels=not args.amp_cast_arm) if amp is not None else 0
     n_amp_conv32 = fuse.use_mixed_disp_conv(model, kernels=not args.amp_cast_arm) if args.amp_conv32 else 0
+    n_cl = fuse.use_channels_last(model.eval()) if args.channels_last else 0
     left, right, _ = steps.synthetic_batch(args.batch, args.height, args.width, args.max_disp, dev)
     for _ in range(args.warmup):
         out = steps.predict(model, left, right, amp)
@@ -91,6 +99,7 @@ def main():
         "miopen_find": bool(args.miopen_find), "params": sum(p.numel() for p in model.parameters()),
         "amp": ("%s, %s (%d call sites)" % (args.amp, "cast arm" if args.amp_cast_arm else "16-bit-storage kernels", n_mixed)) if amp is not None else None,
         "amp_conv32": "MixedDispConv (%d call sites)" % n_amp_conv32 if args.amp_conv32 else False,
+        "channels_last": "ClBnRelu / ClGetCostVolume (%d call sites), PYTORCH_MIOPEN_SUGGEST_NHWC=%s" % (n_cl, os.environ.get("PYTORCH_MIOPEN_SUGGEST_NHWC")) if args.channels_last else False,
         "dtype": ("%s convolutions under autocast, f32 guided aggregation and tails" % args.amp) if amp is not None else "f32", "weights": "random init",
         "disp_range": [round(float(out.min()), 3), round(float(out.max()), 3)],
         "device": torch.cuda.get_device_name(0), "kernel_share": share}))

@@ -23,8 +23,9 @@ def classify(name):
     return "other PyTorch kernels"
 
 
-def profile_passes(fn, passes):
-    """Runs fn() `passes` times under the profiler; returns the share table (per pass)."""
+def profile_passes(fn, passes, watch=("batched_transpose",)):
+    """Runs fn() `passes` times under the profiler; returns the share table (per pass).  `watch`: substrings of kernel names
+    whose summed time is reported on its own (the layout repacking MIOpen does around a convolution)."""
     import torch
     from torch.profiler import ProfilerActivity, profile
     torch.cuda.synchronize()
@@ -49,7 +50,9 @@ def profile_passes(fn, passes):
     if total == 0.0:
         return {"error": "the profiler returned no device events"}
     top = sorted(kernels.items(), key=lambda kv: -kv[1])[:10]
+    watched = {w: sum(v for k, v in kernels.items() if w in k) for w in watch}
     return {"device_ms_per_pass": round(total / passes / 1e3, 3),
+            "watched": {w: {"ms_per_pass": round(v / passes / 1e3, 3), "share": round(v / total, 4)} for w, v in watched.items()},
             "groups": {k: {"ms_per_pass": round(v / passes / 1e3, 3), "share": round(v / total, 4)}
                        for k, v in sorted(groups.items(), key=lambda kv: -kv[1])},
             "top_kernels": [{"ms_per_pass": round(v / passes / 1e3, 3), "name": k[:100]} for k, v in top]}

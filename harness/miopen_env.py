@@ -22,3 +22,10 @@ def use_repo_miopen_cache():
             except OSError:
                 continue
             os.environ[var] = path
+
+
+def suggest_channels_last():
+    """Asks PyTorch-ROCm to hand MIOpen channels-last tensors as they are (PYTORCH_MIOPEN_SUGGEST_NHWC=1) instead of making
+    them planar first, unless the caller has set the switch.  It is read once per process: call this before torch's first
+    convolution.  Returns the value in force."""
+    return os.environ.setdefault("PYTORCH_MIOPEN_SUGGEST_NHWC", "1")

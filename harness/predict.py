@@ -40,6 +40,8 @@ def parse_args(argv=None):
     ap.add_argument("--host_io", action="store_true", help="the reference's host-side numpy front and back end instead of the kernels")
     ap.add_argument("--amp", choices=("bf16", "fp16"), default=None,
                     help="mixed-precision inference: 16-bit convolutions under torch.autocast around the fp32 GA ops (harness.fuse.use_mixed_precision)")
+    ap.add_argument("--channels_last", action="store_true",
+                    help="the cost aggregation on channels_last_3d tensors (harness.fuse.use_channels_last; fp32 inference, implies --fused --fused_bn)")
     ap.add_argument("--amp_cast_arm", action="store_true", help="with --amp: the cast arm (fp32 ops between ATen casts) instead of the 16-bit-storage kernels")
     ap.add_argument("--amp_conv32", action="store_true", help="with --amp: conv32x1 of every Disp / DispAgg on ganet_amd.modules.mixed_conv.MixedDispConv (the HIP kernels on the 16-bit volume; with --amp_cast_arm its cast arm)")
     args = ap.parse_args(argv)
@@ -123,6 +125,11 @@ def main(argv=None):
     args = parse_args(argv)
     from harness.miopen_env import use_repo_miopen_cache
     use_repo_miopen_cache()            # before torch loads MIOpen
+    if args.channels_last:
+        if args.amp is not None:
+            raise SystemExit("--channels_last is fp32 only: it does not compose with --amp")
+        from harness.miopen_env import suggest_channels_last
+        suggest_channels_last()        # before torch's first convolution
     import torch
     from harness import fuse, steps
     assert torch.cuda.is_available(), "harness.predict needs a GPU"
@@ -142,6 +149,7 @@ def main(argv=None):
     amp = {"bf16": torch.bfloat16, "fp16": torch.float16, None: None}[args.amp]
     n_mixed = fuse.use_mixed_precision(model, amp, kernels=not args.amp_cast_arm) if amp is not None else 0
     n_amp_conv32 = fuse.use_mixed_disp_conv(model, kernels=not args.amp_cast_arm) if getattr(args, "amp_conv32", False) else 0
+    n_cl = fuse.use_channels_last(model.eval()) if args.channels_last else 0
 
     def clock():
         torch.cuda.synchronize()
@@ -171,6 +179,7 @@ def main(argv=None):
         "fused_bn": "BnRelu (%d call sites)" % n_fused_bn if args.fused_bn else False,
         "amp": ("%s, %s (%d call sites)" % (args.amp, "cast arm" if args.amp_cast_arm else "16-bit-storage kernels", n_mixed)) if amp is not None else None,
         "amp_conv32": "MixedDispConv (%d call sites)" % n_amp_conv32 if n_amp_conv32 else False,
+        "channels_last": "ClBnRelu / ClGetCostVolume (%d call sites)" % n_cl if n_cl else False,
         "dtype": ("%s convolutions under autocast, f32 guided aggregation and tails" % args.amp) if amp is not None else "f32",
         "ms_io_front": round(1e3 * (t1 - t0), 3), "ms_model_first_call": round(1e3 * (t2 - t1), 3), "ms_io_back": round(1e3 * (t3 - t2), 3),
         "weights": args.resume or "random init", "disp_u16_range": [int(u16.min()), int(u16.max())],
