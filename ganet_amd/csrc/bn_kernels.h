@@ -5,7 +5,7 @@
 // 3 forward (x for the sums, x again, y) and 5 backward (x and grad_y for the sums, both again, grad_x): the backward
 // recomputes the ReLU mask from x, the output is never read back.
 //
-// fp32 tensors [N, C, S] (S = D*H*W or H*W, contiguous slices), 64-bit offsets.  Two launches each way, no atomics:
+// Tensors [N, C, S] (S = D*H*W or H*W, contiguous slices), 64-bit offsets.  Two launches each way, no atomics:
 //   partial sums   grid (R, C): block (r, c) sums its share of channel c into fp64 row r of the caller's workspace
 //                  (per-thread fp64 accumulators, a fixed-order tree through LDS)
 //   apply          the same grid; every block re-sums its channel's R rows in index order (so two runs are bit-identical),
@@ -14,6 +14,16 @@
 // R = Rs * Rn rows: Rs blocks along a slice (at most one trip of BN_BLOCK lanes each before the cap), Rn over the N slices
 // of the channel, R <= min(BN_MAX_ROWS, BN_TARGET_BLOCKS / C): about 2048 blocks on 256 CUs and at most 64 rows to re-sum.
 // V = 4: 16-byte requests (S % 4 == 0 and 16-byte aligned bases); V = 1: the scalar twin.
+//
+// One kernel text for the statistics and for both backward passes; the STORAGE types of the volumes (st_f32 / st_f16 / st_bf16
+// of ga_common.h) are template parameters: Tx of x and gx, Ty of gy; rem and grem are fp32.  All fp32 is the instantiation st_f32
+// at V = 4 | 1.  Under torch.autocast x is 16-bit and gy is x's type, or fp32 in front of an SGABlock (no residual there);
+// statistics, gw and gb stay fp32.  A 16-bit operand is up-cast exactly, the arithmetic below is the same fp32 / fp64 term for
+// term, and a 16-bit result is rounded ONCE on its store; there V = 8 | 1: 16-byte requests of 16-bit storage (S % 8 == 0).  The
+// lanes of V = 8 cover other elements than the lanes of V = 4 do, so the fp64 sums of a mixed call agree with the fp32 entry's to
+// rounding, and bit for bit where every partial sum is exact (tests/mixed_train_cases.py).  The two apply kernels of the forward
+// are fp32 only: their 16-bit forms are siblings (mixed_train_kernels.h: bn_train_apply_mixed, mixed_kernels.h:
+// bn_affine_apply_mixed), which say why.
 //
 // Arithmetic (tests/bn_ref64.py states it in float64):
 //   mean = sum x / M, var = sum x^2 / M - mean^2 (biased), invstd = 1 / sqrt(var + eps), all fp64, M = N * S -- with both
@@ -106,20 +116,20 @@ GA_DEV void bn_sum_rows(const double *__restrict__ ws, int c, int R, double *row
 
 // ---- forward -------------------------------------------------------------------------------------------------------------
 
-template <int V>
+template <typename Tx, int V>
 __global__ void __launch_bounds__(BN_BLOCK)
-bn_stat_partials(const float *__restrict__ x, double *__restrict__ ws, BnGeom g)
+bn_stat_partials(const typename Tx::T *__restrict__ x, double *__restrict__ ws, BnGeom g)
 {
   __shared__ double red[2 * BN_BLOCK];
   const int c = (int)blockIdx.y, rs = (int)blockIdx.x % g.Rs, rn = (int)blockIdx.x / g.Rs;
   const i64 SV = g.S / V, stride = (i64)g.Rs * BN_BLOCK;
-  const double x0 = (double)x[(i64)c * g.S];        // the channel's first value: the origin of both sums
+  const double x0 = (double)Tx::get(x[(i64)c * g.S]);       // the channel's first value: the origin of both sums
   double s1 = 0.0, s2 = 0.0;
   for (int n = rn; n < g.N; n += g.Rn) {
-    const float *xs = x + ((i64)n * g.C + c) * g.S;
+    const typename Tx::T *xs = x + ((i64)n * g.C + c) * g.S;
     for (i64 i = (i64)rs * BN_BLOCK + threadIdx.x; i < SV; i += stride) {
       float a[V];
-      st_load<st_f32, V>(xs + i * V, a);
+      st_load<Tx, V>(xs + i * V, a);
 #pragma unroll
       for (int j = 0; j < V; j++) {
         const double d = (double)a[j] - x0;
@@ -196,9 +206,9 @@ bn_affine_apply(const float *x, const float *__restrict__ rem, const float *__re
 
 // ---- backward ------------------------------------------------------------------------------------------------------------
 
-template <int V>
+template <typename Tx, typename Ty, int V>
 __global__ void __launch_bounds__(BN_BLOCK)
-bn_bwd_partials(const float *__restrict__ x, const float *__restrict__ rem, const float *__restrict__ gy,
+bn_bwd_partials(const typename Tx::T *__restrict__ x, const float *__restrict__ rem, const typename Ty::T *__restrict__ gy,
                 const float *__restrict__ weight, const float *__restrict__ bias, const float *__restrict__ save_mean,
                 const float *__restrict__ save_invstd, double *__restrict__ ws, BnGeom g, int relu)
 {
@@ -214,8 +224,8 @@ bn_bwd_partials(const float *__restrict__ x, const float *__restrict__ rem, cons
     const i64 base = ((i64)n * g.C + c) * g.S;
     for (i64 i = (i64)rs * BN_BLOCK + threadIdx.x; i < SV; i += stride) {
       float a[V], r[V], d[V];
-      st_load<st_f32, V>(x + base + i * V, a);
-      st_load<st_f32, V>(gy + base + i * V, d);
+      st_load<Tx, V>(x + base + i * V, a);
+      st_load<Ty, V>(gy + base + i * V, d);
       if (relu && has_rem) st_load<st_f32, V>(rem + base + i * V, r);
 #pragma unroll
       for (int j = 0; j < V; j++) {
@@ -231,11 +241,11 @@ bn_bwd_partials(const float *__restrict__ x, const float *__restrict__ rem, cons
 
 // gx / grem / gw / gb: nullptr = not wanted.  With neither gx nor grem the launch is one block per channel (the parameter
 // gradients only) and `g` still names the rows the partial sums wrote.
-template <int V>
+template <typename Tx, typename Ty, int V>
 __global__ void __launch_bounds__(BN_BLOCK)
-bn_bwd_apply(const float *__restrict__ x, const float *__restrict__ rem, const float *__restrict__ gy,
+bn_bwd_apply(const typename Tx::T *__restrict__ x, const float *__restrict__ rem, const typename Ty::T *__restrict__ gy,
              const float *__restrict__ weight, const float *__restrict__ bias, const float *__restrict__ save_mean,
-             const float *__restrict__ save_invstd, const double *__restrict__ ws, float *__restrict__ gx,
+             const float *__restrict__ save_invstd, const double *__restrict__ ws, typename Tx::T *__restrict__ gx,
              float *__restrict__ grem, float *__restrict__ gw, float *__restrict__ gb, BnGeom g, int relu)
 {
   BN_FP_STRICT
@@ -260,15 +270,15 @@ bn_bwd_apply(const float *__restrict__ x, const float *__restrict__ rem, const f
     const i64 base = ((i64)n * g.C + c) * g.S;
     for (i64 i = (i64)rs * BN_BLOCK + threadIdx.x; i < SV; i += stride) {
       float a[V], r[V], d[V], o[V];
-      st_load<st_f32, V>(x + base + i * V, a);
-      st_load<st_f32, V>(gy + base + i * V, d);
+      st_load<Tx, V>(x + base + i * V, a);
+      st_load<Ty, V>(gy + base + i * V, d);
       if (relu && has_rem) st_load<st_f32, V>(rem + base + i * V, r);
 #pragma unroll
       for (int j = 0; j < V; j++) {
         if (relu) d[j] = bn_z(a[j], scale, shift, has_rem ? r[j] : 0.f, has_rem) <= 0.f ? 0.f : d[j];
         o[j] = scale * (d[j] - k1 - (a[j] - mean) * q);
       }
-      if (gx) st_store<st_f32, V>(gx + base + i * V, o);
+      if (gx) st_store<Tx, V>(gx + base + i * V, o);
       if (grem) st_store<st_f32, V>(grem + base + i * V, d);
     }
   }

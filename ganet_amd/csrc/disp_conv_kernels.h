@@ -1,5 +1,5 @@
 // disp_conv_kernels.h -- the tails' conv32x1 = nn.Conv3d(C, 1, (3,3,3), (1,1,1), (1,1,1), bias=False) (models/GANet_deep.py:212, 232)
-// as streaming kernels: a reduction over C * 27 taps into ONE output channel, not a GEMM.  fp32, x [N,C,D,H,W], y and gy [N,1,D,H,W],
+// as streaming kernels: a reduction over C * 27 taps into ONE output channel, not a GEMM.  x [N,C,D,H,W], y and gy [N,1,D,H,W],
 // weight [1,C,3,3,3], all contiguous; [.] is zero outside the volume (padding by predication: nothing outside a tensor is read):
 //   forward          y[n,d,h,w]      = sum_c sum_(kd,kh,kw) wgt[c,kd,kh,kw] [x[n,c,d+kd-1,h+kh-1,w+kw-1]]      (disp_conv_fwd)
 //   data gradient    gx[n,c,z,y,x]   = sum_(kd,kh,kw) wgt[c,kd,kh,kw] [gy[n,z-kd+1,y-kh+1,x-kw+1]]              (disp_conv_bwd_data)
@@ -22,6 +22,14 @@
 //                    order in fp64 and rounds once (as bn_kernels.h does its statistics): no atomics, two runs give the same bits.
 // VEC: 16-byte requests (W % 4 == 0 and 16-byte aligned bases); otherwise the 4-byte twin, every word predicated on its own.
 // Every element of y, gx, the workspace rows and gw is written exactly once.  64-bit element offsets throughout.
+//
+// ST, the storage type of the BIG volume (st_f32 / st_f16 / st_bf16 of ga_common.h), is a template parameter of all three: x of
+// the forward and of the weight gradient, gx of the data gradient.  Everything else -- y, gy, the weight, the workspace rows,
+// gw -- is fp32 whatever ST is, and so is all arithmetic: one kernel text per direction, so the 16-bit entries
+// (include/ganet_hip_conv16.h) EQUAL the fp32 entries on the exactly up-cast x by construction.  ST::get is the exact up-cast;
+// ST::put / ST::pack2 round gx ONCE on its store (to nearest even, overflow to +-inf, fp16 subnormals, one quiet NaN).  A 16-bit
+// operand's VEC is one 8-byte request for a lane's four words (W % 4 == 0 and an 8-byte aligned base), its halo words 2-byte
+// loads; its twin predicates every 2-byte word on its own.
 //
 // fp32 roundings on the longest path of one term (tests/disp_conv_ref64.py takes its bound from these; tests/test_sim_disp_conv.py
 // reads them here):
@@ -91,6 +99,52 @@ GA_DEV void dcv_row6(const float *__restrict__ plane, bool ok, int h, int w0, in
   }
 }
 
+// dcv_row6 on a 16-bit plane in two steps, so that the nine requests of a channel's three rows are all issued before the first
+// conversion waits for one of them (a conversion right behind its load costs a memory round trip per request: nine waits per
+// channel and plane in that form, four in this one): the patterns as they were loaded -- 0x0000, zero in both formats, where
+// nothing is read -- and their up-cast afterwards.
+struct Dcv16Row {
+  uint2 own;            // VEC: the lane's four words
+  uint16_t w[6];        // VEC: w[0] and w[5], the halo words; twin: all six
+};
+
+template <bool VEC>
+GA_DEV void dcv16_row6_fetch(const uint16_t *__restrict__ plane, bool ok, int h, int w0, int H, int W, Dcv16Row &r)
+{
+  ok = ok && h >= 0 && h < H;
+  r.own.x = 0u; r.own.y = 0u;
+#pragma unroll
+  for (int j = 0; j < 6; j++) r.w[j] = 0;
+  if (!ok) return;
+  const uint16_t *row = plane + (i64)h * W;
+  if constexpr (VEC) {                  // (w0 % 4 == 0 and W % 4 == 0: the four words are inside)
+    r.own = *reinterpret_cast<const uint2 *>(row + w0);
+    if (w0 > 0) r.w[0] = row[w0 - 1];
+    if (w0 + DCV_PX < W) r.w[5] = row[w0 + DCV_PX];
+  } else {
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+      const int w = w0 - 1 + j;
+      if (w >= 0 && w < W) r.w[j] = row[w];
+    }
+  }
+}
+
+template <typename ST, bool VEC> GA_DEV void dcv16_row6_up(const Dcv16Row &r, float (&v)[6])
+{
+  if constexpr (VEC) {
+    v[0] = ST::get(r.w[0]);
+    v[1] = ST::get((uint16_t)(r.own.x & 0xffffu));
+    v[2] = ST::get((uint16_t)(r.own.x >> 16));
+    v[3] = ST::get((uint16_t)(r.own.y & 0xffffu));
+    v[4] = ST::get((uint16_t)(r.own.y >> 16));
+    v[5] = ST::get(r.w[5]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 6; j++) v[j] = ST::get(r.w[j]);
+  }
+}
+
 // p[i] = row h - 1 + i of plane z of the volume `vol` [D,H,W]; all zero for a plane outside it
 template <bool VEC>
 GA_DEV void dcv_plane(const float *__restrict__ vol, i64 HW, bool ok, int z, int D, int h, int w0, int H, int W, float (&p)[3][6])
@@ -101,16 +155,49 @@ GA_DEV void dcv_plane(const float *__restrict__ vol, i64 HW, bool ok, int z, int
   for (int i = 0; i < 3; i++) dcv_row6<VEC>(plane, ok, h - 1 + i, w0, H, W, p[i]);
 }
 
-// the lane's four words at p (p + 0 .. 3 inside the row for VEC; else each word w0 + k < W on its own)
-template <bool VEC> GA_DEV void dcv_store4(float *p, int w0, int W, const float (&a)[DCV_PX])
+// o = the lane's own four words of an ST volume at p, up-cast, without halo (p + 0 .. 3 inside the row for VEC: one 16- or 8-byte
+// request; else each word w0 + k < W on its own, the others stay as they are)
+template <typename ST, bool VEC> GA_DEV void dcv_own4(const typename ST::T *p, int w0, int W, float (&o)[DCV_PX])
 {
-  if constexpr (VEC) {
-    f4 o; o.x = a[0]; o.y = a[1]; o.z = a[2]; o.w = a[3];
-    *reinterpret_cast<f4 *>(p) = o;
-  } else {
+  if constexpr (!VEC) {
 #pragma unroll
     for (int k = 0; k < DCV_PX; k++)
-      if (w0 + k < W) p[k] = a[k];
+      if (w0 + k < W) o[k] = ST::get(p[k]);
+  } else if constexpr (sizeof(typename ST::T) == 4) {
+    const f4 a = *reinterpret_cast<const f4 *>(p);
+    o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w;
+  } else {
+    const uint2 a = *reinterpret_cast<const uint2 *>(p);
+    o[0] = ST::get((uint16_t)(a.x & 0xffffu));
+    o[1] = ST::get((uint16_t)(a.x >> 16));
+    o[2] = ST::get((uint16_t)(a.y & 0xffffu));
+    o[3] = ST::get((uint16_t)(a.y >> 16));
+  }
+}
+
+// the lane's four words to an ST volume at p, under the same conditions; a 16-bit ST rounds here, once
+template <typename ST, bool VEC> GA_DEV void dcv_store4(typename ST::T *p, int w0, int W, const float (&a)[DCV_PX])
+{
+  if constexpr (sizeof(typename ST::T) == 4) {
+    if constexpr (VEC) {
+      f4 o; o.x = a[0]; o.y = a[1]; o.z = a[2]; o.w = a[3];
+      *reinterpret_cast<f4 *>(p) = o;
+    } else {
+#pragma unroll
+      for (int k = 0; k < DCV_PX; k++)
+        if (w0 + k < W) p[k] = a[k];
+    }
+  } else {
+    if constexpr (VEC) {
+      uint2 o;
+      o.x = ST::pack2(a[0], a[1]);
+      o.y = ST::pack2(a[2], a[3]);
+      *reinterpret_cast<uint2 *>(p) = o;
+    } else {
+#pragma unroll
+      for (int k = 0; k < DCV_PX; k++)
+        if (w0 + k < W) p[k] = ST::put(a[k]);
+    }
   }
 }
 
@@ -129,9 +216,9 @@ GA_DEV void dcv_fma9(const float *__restrict__ wk, const float (&v)[3][6], float
     }
 }
 
-template <bool VEC>
+template <typename ST, bool VEC>
 static __global__ void __launch_bounds__(64 * DCV_WAVES)
-disp_conv_fwd(const float *__restrict__ x, const float *__restrict__ wgt, float *__restrict__ y, DispConvGeom g)
+disp_conv_fwd(const typename ST::T *__restrict__ x, const float *__restrict__ wgt, float *__restrict__ y, DispConvGeom g)
 {
   __shared__ f4 red[2][DCV_WAVES][64];
   const int lane = (int)threadIdx.x & 63, wave = GA_UNIFORM_I((int)threadIdx.x >> 6);
@@ -149,11 +236,20 @@ disp_conv_fwd(const float *__restrict__ x, const float *__restrict__ wgt, float 
       // the planes of y inside the chunk that plane z of x feeds
       const bool k0 = z + 1 < d1, k1 = z >= d0 && z < d1, k2 = z - 1 >= d0;
       for (int c = c0; c < c1; c++) {
-        const float *xs = x + (((i64)n * g.C + c) * g.D + z) * HW;
+        const typename ST::T *xs = x + (((i64)n * g.C + c) * g.D + z) * HW;
         const float *wc = wgt + c * 27;
         float v[3][6];
+        // (this branch stays in the kernel body: behind a helper the compiler schedules every instantiation differently)
+        if constexpr (sizeof(typename ST::T) == 4) {
 #pragma unroll
-        for (int i = 0; i < 3; i++) dcv_row6<VEC>(xs, L.ok, L.h - 1 + i, L.w0, g.H, g.W, v[i]);
+          for (int i = 0; i < 3; i++) dcv_row6<VEC>(xs, L.ok, L.h - 1 + i, L.w0, g.H, g.W, v[i]);
+        } else {
+          Dcv16Row r[3];
+#pragma unroll
+          for (int i = 0; i < 3; i++) dcv16_row6_fetch<VEC>(xs, L.ok, L.h - 1 + i, L.w0, g.H, g.W, r[i]);
+#pragma unroll
+          for (int i = 0; i < 3; i++) dcv16_row6_up<ST, VEC>(r[i], v[i]);
+        }
         if (k0) dcv_fma9(wc, v, A[0]);
         if (k1) dcv_fma9(wc + 9, v, A[1]);
         if (k2) dcv_fma9(wc + 18, v, A[2]);
@@ -173,7 +269,7 @@ disp_conv_fwd(const float *__restrict__ x, const float *__restrict__ wgt, float 
         s[1] = (r0.y + r1.y) + (r2.y + r3.y);
         s[2] = (r0.z + r1.z) + (r2.z + r3.z);
         s[3] = (r0.w + r1.w) + (r2.w + r3.w);
-        dcv_store4<VEC>(y + ((i64)n * g.D + d) * HW + (i64)L.h * g.W + L.w0, L.w0, g.W, s);
+        dcv_store4<st_f32, VEC>(y + ((i64)n * g.D + d) * HW + (i64)L.h * g.W + L.w0, L.w0, g.W, s);
       }
     }
 #pragma unroll
@@ -185,9 +281,9 @@ disp_conv_fwd(const float *__restrict__ x, const float *__restrict__ wgt, float 
 
 // P[j] = plane z - 1 + j of gy around the lane.  Tap (kd, kh, kw) of pixel p reads gy[z - kd + 1, h - kh + 1, w0 + p - kw + 1]
 // = P[2 - kd][2 - kh][p + 2 - kw].
-template <bool VEC>
+template <typename ST, bool VEC>
 static __global__ void __launch_bounds__(64 * DCV_WAVES)
-disp_conv_bwd_data(const float *__restrict__ gy, const float *__restrict__ wgt, float *__restrict__ gx, DispConvGeom g)
+disp_conv_bwd_data(const float *__restrict__ gy, const float *__restrict__ wgt, typename ST::T *__restrict__ gx, DispConvGeom g)
 {
   const int wave = GA_UNIFORM_I((int)threadIdx.x >> 6);
   const DcvLane L = dcv_lane(g);
@@ -215,7 +311,7 @@ disp_conv_bwd_data(const float *__restrict__ gy, const float *__restrict__ wgt, 
 #pragma unroll
             for (int p = 0; p < DCV_PX; p++) a[p] = fmaf(t, P[2 - kd][2 - kh][p + 2 - kw], a[p]);
           }
-      if (L.ok) dcv_store4<VEC>(gx + (((i64)n * g.C + c) * g.D + z) * HW + (i64)L.h * g.W + L.w0, L.w0, g.W, a);
+      if (L.ok) dcv_store4<ST, VEC>(gx + (((i64)n * g.C + c) * g.D + z) * HW + (i64)L.h * g.W + L.w0, L.w0, g.W, a);
     }
 #pragma unroll
     for (int i = 0; i < 3; i++)
@@ -228,9 +324,9 @@ disp_conv_bwd_data(const float *__restrict__ gy, const float *__restrict__ wgt, 
 
 // Row (n, depth chunk, group block) of ws [rows, 27 C]: this workgroup's sums over its 64 groups x DCV_DEPTH planes.  The lane
 // owns the x position: gw[c, kd, kh, kw] += x[c, z, h, w0 + p] gy[z - kd + 1, h - kh + 1, w0 + p - kw + 1], the ring of gy as above.
-template <bool VEC>
+template <typename ST, bool VEC>
 static __global__ void __launch_bounds__(64 * DCV_WAVES)
-disp_conv_bwd_weight_partials(const float *__restrict__ x, const float *__restrict__ gy, float *__restrict__ ws, DispConvGeom g)
+disp_conv_bwd_weight_partials(const typename ST::T *__restrict__ x, const float *__restrict__ gy, float *__restrict__ ws, DispConvGeom g)
 {
   const int lane = (int)threadIdx.x & 63, wave = GA_UNIFORM_I((int)threadIdx.x >> 6);
   const DcvLane L = dcv_lane(g);
@@ -258,17 +354,7 @@ disp_conv_bwd_weight_partials(const float *__restrict__ x, const float *__restri
           float xv[DCV_PX];
 #pragma unroll
           for (int p = 0; p < DCV_PX; p++) xv[p] = 0.f;
-          if (L.ok) {
-            const float *xp = x + (((i64)n * g.C + c) * g.D + z) * HW + (i64)L.h * g.W + L.w0;
-            if constexpr (VEC) {
-              const f4 a = *reinterpret_cast<const f4 *>(xp);
-              xv[0] = a.x; xv[1] = a.y; xv[2] = a.z; xv[3] = a.w;
-            } else {
-#pragma unroll
-              for (int p = 0; p < DCV_PX; p++)
-                if (L.w0 + p < g.W) xv[p] = xp[p];
-            }
-          }
+          if (L.ok) dcv_own4<ST, VEC>(x + (((i64)n * g.C + c) * g.D + z) * HW + (i64)L.h * g.W + L.w0, L.w0, g.W, xv);
 #pragma unroll
           for (int kd = 0; kd < 3; kd++)
 #pragma unroll

@@ -9,7 +9,6 @@
 #include "misc_kernels.h"
 #include "disp_tail_kernels.h"
 #include "disp_conv_kernels.h"
-#include "disp_conv16_kernels.h"
 #include "cl_kernels.h"
 #include "mixed_kernels.h"
 #include "mixed_train_kernels.h"
@@ -1486,6 +1485,49 @@ int check_disp_conv(const char *who, int N, int C, int D, int H, int W, DispConv
   return GANET_OK;
 }
 i64 disp_conv_rows(const dim3 &grid) { return (i64)grid.x * grid.y * grid.z; }
+bool type16(int t) { return t == GANET_F16 || t == GANET_BF16; }
+
+// The launch of each direction, once, behind the entry of every storage type ST of the big volume (x, grad_x): the entry has
+// checked its operands and decides `vec`; `what` is its name for the launch.
+template <typename ST>
+int launch_disp_conv_fwd(const void *x, const float *weight, float *y, const DispConvGeom &g, dim3 grid, bool vec, void *stream,
+                         const char *what)
+{
+  with_flags([&](auto v) {
+    GA_LAUNCH((disp_conv_fwd<ST, decltype(v)::value>), grid, dim3(64 * DCV_WAVES), (hipStream_t)stream, (const typename ST::T *)x, weight, y, g);
+  }, vec);
+  return check_launch(what);
+}
+
+template <typename ST>
+int launch_disp_conv_bwd_data(const float *grad_y, const float *weight, void *grad_x, const DispConvGeom &g, dim3 grid, bool vec,
+                              void *stream, const char *what)
+{
+  with_flags([&](auto v) {
+    GA_LAUNCH((disp_conv_bwd_data<ST, decltype(v)::value>), grid, dim3(64 * DCV_WAVES), (hipStream_t)stream, grad_y, weight,
+              (typename ST::T *)grad_x, g);
+  }, vec);
+  return check_launch(what);
+}
+
+// ... and the second stage: the workspace rows added up in fp64
+template <typename ST>
+int launch_disp_conv_bwd_weight(const char *who, const void *x, const float *grad_y, float *workspace, float *grad_weight,
+                                const DispConvGeom &g, dim3 grid, bool vec, void *stream, const char *what)
+{
+  const i64 rows = disp_conv_rows(grid);
+  if (rows * 27 * g.C > 0x7fffffff) return fail(GANET_E_UNSUPPORTED, "%s: the workspace is beyond ganet_disp_conv_workspace's answer", who);
+  hipStream_t st = (hipStream_t)stream;
+  with_flags([&](auto v) {
+    GA_LAUNCH((disp_conv_bwd_weight_partials<ST, decltype(v)::value>), grid, dim3(64 * DCV_WAVES), st, (const typename ST::T *)x, grad_y,
+              workspace, g);
+  }, vec);
+  GA_TRY(check_launch(what));
+  const int K = 27 * g.C;
+  GA_LAUNCH(disp_conv_bwd_weight_sum, dim3((unsigned)((K + DCV_SUM_COLS - 1) / DCV_SUM_COLS)),
+            dim3(DCV_SUM_COLS * DCV_SUM_SLICES), st, (const float *)workspace, grad_weight, K, rows);
+  return check_launch("disp conv backward (weight sum)");
+}
 }  // namespace
 
 GA_EXPORT int ganet_disp_conv_workspace(int N, int C, int D, int H, int W)
@@ -1508,10 +1550,7 @@ GA_EXPORT int ganet_disp_conv_forward(const float *x, const float *weight, float
   dim3 grid;
   GA_TRY(check_disp_conv(who, N, C, D, H, W, g, grid));
   if (y == x || y == weight) return fail(GANET_E_INVALID, "%s: y must not alias an input", who);
-  const dim3 block(64 * DCV_WAVES);
-  with_flags([&](auto v) { GA_LAUNCH((disp_conv_fwd<decltype(v)::value>), grid, block, (hipStream_t)stream, x, weight, y, g); },
-             W % 4 == 0 && aligned16(x, y));
-  return check_launch("disp conv forward");
+  return launch_disp_conv_fwd<st_f32>(x, weight, y, g, grid, W % 4 == 0 && aligned16(x, y), stream, "disp conv forward");
 }
 
 GA_EXPORT int ganet_disp_conv_backward_data(const float *grad_y, const float *weight, float *grad_x, int N, int C, int D,
@@ -1523,10 +1562,8 @@ GA_EXPORT int ganet_disp_conv_backward_data(const float *grad_y, const float *we
   dim3 grid;
   GA_TRY(check_disp_conv(who, N, C, D, H, W, g, grid));
   if (grad_x == grad_y || grad_x == weight) return fail(GANET_E_INVALID, "%s: grad_x must not alias an input", who);
-  const dim3 block(64 * DCV_WAVES);
-  with_flags([&](auto v) { GA_LAUNCH((disp_conv_bwd_data<decltype(v)::value>), grid, block, (hipStream_t)stream, grad_y, weight, grad_x, g); },
-             W % 4 == 0 && aligned16(grad_y, grad_x));
-  return check_launch("disp conv backward (data)");
+  return launch_disp_conv_bwd_data<st_f32>(grad_y, weight, grad_x, g, grid, W % 4 == 0 && aligned16(grad_y, grad_x), stream,
+                                           "disp conv backward (data)");
 }
 
 GA_EXPORT int ganet_disp_conv_backward_weight(const float *x, const float *grad_y, float *workspace, float *grad_weight,
@@ -1539,17 +1576,8 @@ GA_EXPORT int ganet_disp_conv_backward_weight(const float *x, const float *grad_
   GA_TRY(check_disp_conv(who, N, C, D, H, W, g, grid));
   if (grad_weight == x || grad_weight == grad_y || workspace == x || workspace == grad_y || workspace == grad_weight)
     return fail(GANET_E_INVALID, "%s: workspace and grad_weight must not alias anything", who);
-  const i64 rows = disp_conv_rows(grid);
-  if (rows * 27 * C > 0x7fffffff) return fail(GANET_E_UNSUPPORTED, "%s: the workspace is beyond ganet_disp_conv_workspace's answer", who);
-  const dim3 block(64 * DCV_WAVES);
-  hipStream_t st = (hipStream_t)stream;
-  with_flags([&](auto v) { GA_LAUNCH((disp_conv_bwd_weight_partials<decltype(v)::value>), grid, block, st, x, grad_y, workspace, g); },
-             W % 4 == 0 && aligned16(x, grad_y));
-  GA_TRY(check_launch("disp conv backward (weight partials)"));
-  const int K = 27 * C;
-  GA_LAUNCH(disp_conv_bwd_weight_sum, dim3((unsigned)((K + DCV_SUM_COLS - 1) / DCV_SUM_COLS)),
-            dim3(DCV_SUM_COLS * DCV_SUM_SLICES), st, (const float *)workspace, grad_weight, K, rows);
-  return check_launch("disp conv backward (weight sum)");
+  return launch_disp_conv_bwd_weight<st_f32>(who, x, grad_y, workspace, grad_weight, g, grid, W % 4 == 0 && aligned16(x, grad_y), stream,
+                                             "disp conv backward (weight partials)");
 }
 
 // ---- SGABlock's residual epilogue (models/GANet_deep.py:270-277) --------------------
@@ -1698,6 +1726,84 @@ float bn_float(int bits)
   memcpy(&f, &bits, sizeof f);
   return f;
 }
+
+// The launches of each pass, once, behind the entries of every storage type (bn_kernels.h: Tx of x and grad_x, Ty of y and
+// grad_y; Tr of the affine form's rem).  The entry has checked its operands, made g for V elements per lane and names its
+// launches (what_*) for check_launch.
+struct BnForwardArgs {
+  const void *x;
+  const float *rem, *weight, *bias;
+  float *running_mean, *running_var;
+  double *workspace;
+  void *y;
+  float *save_mean, *save_invstd;
+  int momentum_bits, eps_bits, relu;
+  void *stream;
+  const char *what_sums, *what_apply;
+};
+
+template <typename Tx, typename Ty, int V>
+int launch_bn_train_forward(const BnForwardArgs &a, const BnGeom &g)
+{
+  const typename Tx::T *xp = (const typename Tx::T *)a.x;
+  const float momentum = bn_float(a.momentum_bits), eps = bn_float(a.eps_bits);
+  const dim3 grid(g.Rs * g.Rn, g.C);
+  hipStream_t st = (hipStream_t)a.stream;
+  GA_LAUNCH((bn_stat_partials<Tx, V>), grid, dim3(BN_BLOCK), st, xp, a.workspace, g);
+  GA_TRY(check_launch(a.what_sums));
+  // (the apply pass of a 16-bit x is a sibling kernel: mixed_train_kernels.h says why)
+  if constexpr (std::is_same_v<Tx, st_f32>)
+    GA_LAUNCH((bn_train_apply<V>), grid, dim3(BN_BLOCK), st, xp, a.rem, a.weight, a.bias, a.running_mean, a.running_var, a.workspace,
+              (float *)a.y, a.save_mean, a.save_invstd, g, momentum, eps, a.relu);
+  else
+    GA_LAUNCH((bn_train_apply_mixed<Tx, Ty, V>), grid, dim3(BN_BLOCK), st, xp, a.rem, a.weight, a.bias, a.running_mean, a.running_var,
+              a.workspace, (typename Ty::T *)a.y, a.save_mean, a.save_invstd, g, momentum, eps, a.relu);
+  return check_launch(a.what_apply);
+}
+
+struct BnBackwardArgs {
+  const void *x;
+  const float *rem;
+  const void *grad_y;
+  const float *weight, *bias, *save_mean, *save_invstd;
+  double *workspace;
+  void *grad_x;
+  float *grad_rem, *grad_weight, *grad_bias;
+  int relu;
+  void *stream;
+  const char *what_sums, *what_apply;
+};
+
+template <typename Tx, typename Ty, int V>
+int launch_bn_train_backward(const BnBackwardArgs &a, const BnGeom &g)
+{
+  if (!a.grad_x && !a.grad_rem && !a.grad_weight && !a.grad_bias) return GANET_OK;
+  const typename Tx::T *xp = (const typename Tx::T *)a.x;
+  const typename Ty::T *gp = (const typename Ty::T *)a.grad_y;
+  const dim3 grid(g.Rs * g.Rn, g.C), apply_grid = (a.grad_x || a.grad_rem) ? grid : dim3(1, g.C);
+  hipStream_t st = (hipStream_t)a.stream;
+  GA_LAUNCH((bn_bwd_partials<Tx, Ty, V>), grid, dim3(BN_BLOCK), st, xp, a.rem, gp, a.weight, a.bias, a.save_mean, a.save_invstd, a.workspace,
+            g, a.relu);
+  GA_TRY(check_launch(a.what_sums));
+  GA_LAUNCH((bn_bwd_apply<Tx, Ty, V>), apply_grid, dim3(BN_BLOCK), st, xp, a.rem, gp, a.weight, a.bias, a.save_mean, a.save_invstd,
+            a.workspace, (typename Tx::T *)a.grad_x, a.grad_rem, a.grad_weight, a.grad_bias, g, a.relu);
+  return check_launch(a.what_apply);
+}
+
+// (the all-fp32 form and the forms with a 16-bit operand are sibling kernels: mixed_kernels.h says why)
+template <typename Tx, typename Tr, typename Ty, int V>
+int launch_bn_affine(const void *x, const void *rem, const float *scale, const float *shift, void *y, const BnGeom &g, int relu,
+                     void *stream, const char *what)
+{
+  const dim3 grid(g.Rs * g.Rn, g.C);
+  hipStream_t st = (hipStream_t)stream;
+  if constexpr (std::is_same_v<Tx, st_f32> && std::is_same_v<Tr, st_f32> && std::is_same_v<Ty, st_f32>)
+    GA_LAUNCH((bn_affine_apply<V>), grid, dim3(BN_BLOCK), st, (const float *)x, (const float *)rem, scale, shift, (float *)y, g, relu);
+  else
+    GA_LAUNCH((bn_affine_apply_mixed<Tx, Tr, Ty, V>), grid, dim3(BN_BLOCK), st, (const typename Tx::T *)x, (const typename Tr::T *)rem,
+              scale, shift, (typename Ty::T *)y, g, relu);
+  return check_launch(what);
+}
 }  // namespace
 
 GA_EXPORT int ganet_bn_workspace(int N, int C, int S)
@@ -1719,18 +1825,10 @@ GA_EXPORT int ganet_bn_train_forward(const float *x, const float *rem, const flo
   const bool vec = S % 4 == 0 && aligned16(x, y, rem);
   BnGeom g;
   GA_TRY(bn_geom(who, N, C, S, vec ? 4 : 1, true, &g));
-  const float momentum = bn_float(momentum_bits), eps = bn_float(eps_bits);
-  const dim3 grid(g.Rs * g.Rn, C);
-  hipStream_t st = (hipStream_t)stream;
+  const BnForwardArgs a = {x, rem, weight, bias, running_mean, running_var, workspace, y, save_mean, save_invstd, momentum_bits, eps_bits,
+                           relu, stream, "batch norm statistics", "batch norm forward"};
   int rc;
-  with_width<4>(vec, [&](auto v) {
-    constexpr int V = decltype(v)::value;
-    GA_LAUNCH((bn_stat_partials<V>), grid, dim3(BN_BLOCK), st, x, workspace, g);
-    if ((rc = check_launch("batch norm statistics")) != GANET_OK) return;
-    GA_LAUNCH((bn_train_apply<V>), grid, dim3(BN_BLOCK), st, x, rem, weight, bias, running_mean, running_var, workspace, y,
-              save_mean, save_invstd, g, momentum, eps, relu);
-    rc = check_launch("batch norm forward");
-  });
+  with_width<4>(vec, [&](auto v) { rc = launch_bn_train_forward<st_f32, st_f32, decltype(v)::value>(a, g); });
   return rc;
 }
 
@@ -1747,18 +1845,10 @@ GA_EXPORT int ganet_bn_train_backward(const float *x, const float *rem, const fl
   const bool vec = S % 4 == 0 && aligned16(x, rem, grad_y, grad_x, grad_rem);
   BnGeom g;
   GA_TRY(bn_geom(who, N, C, S, vec ? 4 : 1, true, &g));
-  if (!grad_x && !grad_rem && !grad_weight && !grad_bias) return GANET_OK;
-  const dim3 grid(g.Rs * g.Rn, C), apply_grid = (grad_x || grad_rem) ? grid : dim3(1, C);
-  hipStream_t st = (hipStream_t)stream;
+  const BnBackwardArgs a = {x, rem, grad_y, weight, bias, save_mean, save_invstd, workspace, grad_x, grad_rem, grad_weight, grad_bias, relu,
+                            stream, "batch norm backward sums", "batch norm backward"};
   int rc;
-  with_width<4>(vec, [&](auto v) {
-    constexpr int V = decltype(v)::value;
-    GA_LAUNCH((bn_bwd_partials<V>), grid, dim3(BN_BLOCK), st, x, rem, grad_y, weight, bias, save_mean, save_invstd, workspace, g, relu);
-    if ((rc = check_launch("batch norm backward sums")) != GANET_OK) return;
-    GA_LAUNCH((bn_bwd_apply<V>), apply_grid, dim3(BN_BLOCK), st, x, rem, grad_y, weight, bias, save_mean, save_invstd, workspace,
-              grad_x, grad_rem, grad_weight, grad_bias, g, relu);
-    rc = check_launch("batch norm backward");
-  });
+  with_width<4>(vec, [&](auto v) { rc = launch_bn_train_backward<st_f32, st_f32, decltype(v)::value>(a, g); });
   return rc;
 }
 
@@ -1771,10 +1861,11 @@ GA_EXPORT int ganet_bn_apply_forward(const float *x, const float *rem, const flo
   const bool vec = S % 4 == 0 && aligned16(x, y, rem);
   BnGeom g;
   GA_TRY(bn_geom(who, N, C, S, vec ? 4 : 1, false, &g));
-  const dim3 grid(g.Rs * g.Rn, C);
-  hipStream_t st = (hipStream_t)stream;
-  with_width<4>(vec, [&](auto V) { GA_LAUNCH((bn_affine_apply<decltype(V)::value>), grid, dim3(BN_BLOCK), st, x, rem, scale, shift, y, g, relu); });
-  return check_launch("batch norm apply");
+  int rc;
+  with_width<4>(vec, [&](auto v) {
+    rc = launch_bn_affine<st_f32, st_f32, st_f32, decltype(v)::value>(x, rem, scale, shift, y, g, relu, stream, "batch norm apply");
+  });
+  return rc;
 }
 
 // ---- mixed precision: 16-bit storage around the fp32 ops (mixed_kernels.h) ----------------------------------------------------
@@ -1836,8 +1927,7 @@ GA_EXPORT int ganet_bn_apply_forward_mixed(const void *x, const void *rem, const
   const bool vec = S % MX_V == 0 && aligned16(x, y, rem);
   BnGeom g;
   GA_TRY(bn_geom(who, N, C, S, vec ? MX_V : 1, false, &g));
-  const dim3 grid(g.Rs * g.Rn, C);
-  hipStream_t st = (hipStream_t)stream;
+  int rc = GANET_OK;
   // the 16-bit format of the call (x's, or y's under an fp32 x); every operand is that or fp32
   with_st16(x32 ? y_type : x_type, [&](auto t16) {
     with_flags([&](auto fx, auto r16, auto o16, auto v) {
@@ -1847,11 +1937,10 @@ GA_EXPORT int ganet_bn_apply_forward_mixed(const void *x, const void *rem, const
       using Ty = std::conditional_t<decltype(o16)::value, T16, st_f32>;
       // (an fp32 x has an fp32 rem and a 16-bit y: checked above)
       if constexpr (!decltype(fx)::value || (!decltype(r16)::value && decltype(o16)::value))
-        GA_LAUNCH((bn_affine_apply_mixed<Tx, Tr, Ty, decltype(v)::value ? MX_V : 1>), grid, dim3(BN_BLOCK), st, (const typename Tx::T *)x,
-                  (const typename Tr::T *)rem, scale, shift, (typename Ty::T *)y, g, relu);
+        rc = launch_bn_affine<Tx, Tr, Ty, decltype(v)::value ? MX_V : 1>(x, rem, scale, shift, y, g, relu, stream, "batch norm apply (mixed)");
     }, x32, rem16, y16, vec);
   });
-  return check_launch("batch norm apply (mixed)");
+  return rc;
 }
 
 GA_EXPORT int ganet_cost_volume_forward_16(const void *x, const void *y, void *cost, int N, int C, int Dn, int H, int W,
@@ -1897,7 +1986,7 @@ GA_EXPORT int ganet_l1_normalize_forward_mixed(const void *x, float *y0, float *
   return check_launch("l1 normalise forward (mixed)");
 }
 
-// ---- mixed precision, training: batch statistics and the backwards on 16-bit storage (mixed_train_kernels.h) -------------------
+// ---- mixed precision, training: batch statistics and the backwards on 16-bit storage (bn_kernels.h, mixed_train_kernels.h) -----
 namespace {
 // the three sites of a model under autocast: x 16-bit; y (grad_y) in x's format with an fp32 residual or none, or fp32 with none
 int check_bn_mixed_types(const char *who, const void *rem, int x_type, int rem_type, int y_type)
@@ -1926,20 +2015,14 @@ GA_EXPORT int ganet_bn_train_forward_mixed(const void *x, const float *rem, cons
   const bool vec = S % MX_V == 0 && aligned16(x, y, rem);
   BnGeom g;
   GA_TRY(bn_geom(who, N, C, S, vec ? MX_V : 1, true, &g));
-  const float momentum = bn_float(momentum_bits), eps = bn_float(eps_bits);
-  const dim3 grid(g.Rs * g.Rn, C);
-  hipStream_t st = (hipStream_t)stream;
+  const BnForwardArgs a = {x, rem, weight, bias, running_mean, running_var, workspace, y, save_mean, save_invstd, momentum_bits, eps_bits,
+                           relu, stream, "batch norm statistics (mixed)", "batch norm forward (mixed)"};
   int rc;
   with_st16(x_type, [&](auto t16) {
     with_flags([&](auto o16, auto v) {
       using Tx = typename decltype(t16)::type;
       using Ty = std::conditional_t<decltype(o16)::value, Tx, st_f32>;
-      constexpr int V = decltype(v)::value ? MX_V : 1;
-      GA_LAUNCH((bn_stat_partials_mixed<Tx, V>), grid, dim3(BN_BLOCK), st, (const typename Tx::T *)x, workspace, g);
-      if ((rc = check_launch("batch norm statistics (mixed)")) != GANET_OK) return;
-      GA_LAUNCH((bn_train_apply_mixed<Tx, Ty, V>), grid, dim3(BN_BLOCK), st, (const typename Tx::T *)x, rem, weight, bias, running_mean,
-                running_var, workspace, (typename Ty::T *)y, save_mean, save_invstd, g, momentum, eps, relu);
-      rc = check_launch("batch norm forward (mixed)");
+      rc = launch_bn_train_forward<Tx, Ty, decltype(v)::value ? MX_V : 1>(a, g);
     }, y_type != GANET_F32, vec);
   });
   return rc;
@@ -1959,22 +2042,14 @@ GA_EXPORT int ganet_bn_train_backward_mixed(const void *x, const float *rem, con
   const bool vec = S % MX_V == 0 && aligned16(x, rem, grad_y, grad_x, grad_rem);
   BnGeom g;
   GA_TRY(bn_geom(who, N, C, S, vec ? MX_V : 1, true, &g));
-  if (!grad_x && !grad_rem && !grad_weight && !grad_bias) return GANET_OK;
-  const dim3 grid(g.Rs * g.Rn, C), apply_grid = (grad_x || grad_rem) ? grid : dim3(1, C);
-  hipStream_t st = (hipStream_t)stream;
+  const BnBackwardArgs a = {x, rem, grad_y, weight, bias, save_mean, save_invstd, workspace, grad_x, grad_rem, grad_weight, grad_bias, relu,
+                            stream, "batch norm backward sums (mixed)", "batch norm backward (mixed)"};
   int rc;
   with_st16(x_type, [&](auto t16) {
     with_flags([&](auto o16, auto v) {
       using Tx = typename decltype(t16)::type;
       using Ty = std::conditional_t<decltype(o16)::value, Tx, st_f32>;
-      constexpr int V = decltype(v)::value ? MX_V : 1;
-      const typename Tx::T *xp = (const typename Tx::T *)x;
-      const typename Ty::T *gp = (const typename Ty::T *)grad_y;
-      GA_LAUNCH((bn_bwd_partials_mixed<Tx, Ty, V>), grid, dim3(BN_BLOCK), st, xp, rem, gp, weight, bias, save_mean, save_invstd, workspace, g, relu);
-      if ((rc = check_launch("batch norm backward sums (mixed)")) != GANET_OK) return;
-      GA_LAUNCH((bn_bwd_apply_mixed<Tx, Ty, V>), apply_grid, dim3(BN_BLOCK), st, xp, rem, gp, weight, bias, save_mean, save_invstd, workspace,
-                (typename Tx::T *)grad_x, grad_rem, grad_weight, grad_bias, g, relu);
-      rc = check_launch("batch norm backward (mixed)");
+      rc = launch_bn_train_backward<Tx, Ty, decltype(v)::value ? MX_V : 1>(a, g);
     }, gy_type != GANET_F32, vec);
   });
   return rc;
@@ -2197,11 +2272,7 @@ GA_EXPORT int ganet_selftest_dpp(int *scratch_dev, int *host_out, void *stream)
   });
 }
 
-// ---- conv32x1 on a 16-bit x (include/ganet_hip_conv16.h; disp_conv16_kernels.h) -----------------------------------------------
-namespace {
-bool type16(int t) { return t == GANET_F16 || t == GANET_BF16; }
-}  // namespace
-
+// ---- conv32x1 on a 16-bit x (include/ganet_hip_conv16.h; disp_conv_kernels.h with a 16-bit ST) -------------------------------------
 GA_EXPORT int ganet_disp_conv_forward_16(const void *x, const float *weight, float *y, int N, int C, int D, int H, int W,
                                          int x_type, void *stream)
 {
@@ -2212,14 +2283,12 @@ GA_EXPORT int ganet_disp_conv_forward_16(const void *x, const float *weight, flo
   GA_TRY(check_disp_conv(who, N, C, D, H, W, g, grid));
   if (!type16(x_type)) return fail(GANET_E_INVALID, "%s: type code %d (fp16 or bf16)", who, x_type);
   if ((const void *)y == x || y == weight) return fail(GANET_E_INVALID, "%s: y must not alias an input", who);
-  const dim3 block(64 * DCV_WAVES);
-  const uint16_t *xp = (const uint16_t *)x;
+  int rc;
   with_st16(x_type, [&](auto t) {
-    using ST = typename decltype(t)::type;
-    with_flags([&](auto v) { GA_LAUNCH((disp_conv16_fwd<ST, decltype(v)::value>), grid, block, (hipStream_t)stream, xp, weight, y, g); },
-               W % 4 == 0 && aligned8(xp) && aligned16(y));
+    rc = launch_disp_conv_fwd<typename decltype(t)::type>(x, weight, y, g, grid, W % 4 == 0 && aligned8(x) && aligned16(y), stream,
+                                                          "disp conv forward (16-bit x)");
   });
-  return check_launch("disp conv forward (16-bit x)");
+  return rc;
 }
 
 GA_EXPORT int ganet_disp_conv_backward_data_16(const float *grad_y, const float *weight, void *grad_x, int N, int C, int D,
@@ -2232,14 +2301,12 @@ GA_EXPORT int ganet_disp_conv_backward_data_16(const float *grad_y, const float 
   GA_TRY(check_disp_conv(who, N, C, D, H, W, g, grid));
   if (!type16(gx_type)) return fail(GANET_E_INVALID, "%s: type code %d (fp16 or bf16)", who, gx_type);
   if (grad_x == (const void *)grad_y || grad_x == (const void *)weight) return fail(GANET_E_INVALID, "%s: grad_x must not alias an input", who);
-  const dim3 block(64 * DCV_WAVES);
-  uint16_t *gp = (uint16_t *)grad_x;
+  int rc;
   with_st16(gx_type, [&](auto t) {
-    using ST = typename decltype(t)::type;
-    with_flags([&](auto v) { GA_LAUNCH((disp_conv16_bwd_data<ST, decltype(v)::value>), grid, block, (hipStream_t)stream, grad_y, weight, gp, g); },
-               W % 4 == 0 && aligned8(gp) && aligned16(grad_y));
+    rc = launch_disp_conv_bwd_data<typename decltype(t)::type>(grad_y, weight, grad_x, g, grid, W % 4 == 0 && aligned8(grad_x) && aligned16(grad_y),
+                                                               stream, "disp conv backward (data, 16-bit grad_x)");
   });
-  return check_launch("disp conv backward (data, 16-bit grad_x)");
+  return rc;
 }
 
 GA_EXPORT int ganet_disp_conv_backward_weight_16(const void *x, const float *grad_y, float *workspace, float *grad_weight,
@@ -2253,21 +2320,13 @@ GA_EXPORT int ganet_disp_conv_backward_weight_16(const void *x, const float *gra
   if (!type16(x_type)) return fail(GANET_E_INVALID, "%s: type code %d (fp16 or bf16)", who, x_type);
   if ((const void *)grad_weight == x || grad_weight == grad_y || (const void *)workspace == x || workspace == grad_y || workspace == grad_weight)
     return fail(GANET_E_INVALID, "%s: workspace and grad_weight must not alias anything", who);
-  const i64 rows = disp_conv_rows(grid);
-  if (rows * 27 * C > 0x7fffffff) return fail(GANET_E_UNSUPPORTED, "%s: the workspace is beyond ganet_disp_conv_workspace's answer", who);
-  const dim3 block(64 * DCV_WAVES);
-  hipStream_t st = (hipStream_t)stream;
-  const uint16_t *xp = (const uint16_t *)x;
+  int rc;
   with_st16(x_type, [&](auto t) {
-    using ST = typename decltype(t)::type;
-    with_flags([&](auto v) { GA_LAUNCH((disp_conv16_bwd_weight_partials<ST, decltype(v)::value>), grid, block, st, xp, grad_y, workspace, g); },
-               W % 4 == 0 && aligned8(xp) && aligned16(grad_y));
+    rc = launch_disp_conv_bwd_weight<typename decltype(t)::type>(who, x, grad_y, workspace, grad_weight, g, grid,
+                                                                 W % 4 == 0 && aligned8(x) && aligned16(grad_y), stream,
+                                                                 "disp conv backward (weight partials, 16-bit x)");
   });
-  GA_TRY(check_launch("disp conv backward (weight partials, 16-bit x)"));
-  const int K = 27 * C;
-  GA_LAUNCH(disp_conv_bwd_weight_sum, dim3((unsigned)((K + DCV_SUM_COLS - 1) / DCV_SUM_COLS)),
-            dim3(DCV_SUM_COLS * DCV_SUM_SLICES), st, (const float *)workspace, grad_weight, K, rows);
-  return check_launch("disp conv backward (weight sum)");
+  return rc;
 }
 
 // ---- the channels-last inference path (include/ganet_hip_cl.h; cl_kernels.h) ---------------------------------------------------

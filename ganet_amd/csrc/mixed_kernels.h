@@ -1,7 +1,7 @@
 // mixed_kernels.h -- the streaming kernels that sit between a 16-bit convolution and an fp32 guided-aggregation op, for gfx950.
 // Under torch.autocast MIOpen's convolutions read and write fp16 / bf16; SGA, LGA and the tails stay fp32.  These kernels read
 // and write 16-bit STORAGE (ga_common.h: st_f16 / st_bf16, uint16_t patterns) and compute in fp32, so that no cast pass stands
-// between a convolution and one of our ops.  Forward only (inference).
+// between a convolution and one of our ops.
 //
 // The contract (tests/mixed_cases.py): with 16-bit inputs a16, ...
 //     op_mixed(a16, ...) == convert(op_fp32(upcast(a16), ...), out_type)            bit for bit, NaN positions equal
@@ -12,6 +12,9 @@
 //                           y 16-bit | f32; also x f32, rem none | f32, y 16-bit (behind an op autocast keeps in fp32).
 //                           bn_affine_apply's grid and slice loop (BnGeom) with eight elements per lane.
 //                           y may BE x where both have one width: a lane reads its eight elements before it writes them.
+//                           A sibling of bn_affine_apply, not one template with it: folded into bn_apply_share's form its
+//                           V = 8 instantiations need one more SGPR each (profiles/r24a_kernel_resources.txt).
+//                           The TRAINING forms of the 16-bit site are bn_kernels.h's own kernels on 16-bit storage types.
 //   cost_volume_fwd16       GetCostVolume on 2-byte elements: a copy with zeros, and 0x0000 is zero in both formats -- no type.
 //                           Its scalar twin is misc_kernels.h's cost_volume_fwd<uint16_t>.
 //   l1norm_fwd<KT, Tx>      misc_kernels.h's kernel itself, reading a 16-bit x; fp32 outputs.

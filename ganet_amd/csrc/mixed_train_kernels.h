@@ -1,20 +1,8 @@
-// mixed_train_kernels.h -- what a TRAINING step under torch.autocast needs beside mixed_kernels.h, for gfx950: batch statistics
-// on 16-bit storage, the backward of the 16-bit BatchNorm site and the adjoint of the 16-bit cost volume.  (The backward of the
-// 16-bit L1 normalisation is misc_kernels.h's l1norm_bwd<KT, Tx> itself.)  16-bit STORAGE (ga_common.h: st_f16 / st_bf16), fp32
-// and fp64 arithmetic: every operand is up-cast exactly, every 16-bit result is rounded ONCE on its store.
-//
-// BatchNorm + residual + ReLU in training mode: bn_kernels.h's arithmetic term for term (its header states it; tests/bn_ref64.py
-// in float64) -- fp64 sums over d = x - x0, mean and invstd rounded to fp32 once, bn_z and relu_keep_nan, the backward's mask
-// recomputed from x, k1 and q rounded once each, the running statistics in fp64 and written once -- and its structure: two
-// launches each way over one BnGeom grid, fp64 rows in the caller's workspace, re-summed in index order by every block, no
-// atomics.  Siblings of the fp32 kernels, not one template with them: those stay as they are, instruction for instruction.
-//   x       16-bit (Tx); saved for the backward, so there is no in-place form
-//   rem     fp32 or none (the SGABlock tail adds the fp32 SGA output to a 16-bit convolution)
-//   y, gy   Ty: 16-bit, or fp32 in front of an SGABlock (no residual there)
-//   gx      Tx;  grem fp32;  statistics, running buffers, gw and gb fp32
-// V = 8: 16-byte requests of 16-bit storage (S % 8 == 0, 16-byte aligned bases); V = 1: the scalar twin.  The lanes of V = 8
-// cover other elements than bn_kernels.h's V = 4 lanes do, so the fp64 sums agree with the fp32 entry's to rounding, and bit
-// for bit where every partial sum is exact (tests/mixed_train_cases.py).
+// mixed_train_kernels.h -- the adjoint of the 16-bit cost volume, which a TRAINING step under torch.autocast needs beside
+// mixed_kernels.h, for gfx950, and the apply pass of the 16-bit BatchNorm site's forward.  (Its batch statistics and its backward are
+// bn_kernels.h's kernels on 16-bit storage types; the backward of the 16-bit L1 normalisation is misc_kernels.h's
+// l1norm_bwd<KT, Tx>.)  16-bit STORAGE (ga_common.h: st_f16 / st_bf16), fp32 and fp64 arithmetic: every operand is up-cast exactly, every
+// 16-bit result is rounded ONCE on its store.
 //
 // cost_volume_bwd16: misc_kernels.h's cost_volume_bwd on 16-bit gcost / gx / gy; fp32 sums over i ascending, masked adds.
 #pragma once
@@ -22,33 +10,13 @@
 
 namespace ga {
 
-// ---- BatchNorm forward -------------------------------------------------------------------------------------------------------
+// ---- BatchNorm forward, the apply pass on a 16-bit x -------------------------------------------------------------------------
 
-template <typename Tx, int V>
-__global__ void __launch_bounds__(BN_BLOCK)
-bn_stat_partials_mixed(const typename Tx::T *__restrict__ x, double *__restrict__ ws, BnGeom g)
-{
-  __shared__ double red[2 * BN_BLOCK];
-  const int c = (int)blockIdx.y, rs = (int)blockIdx.x % g.Rs, rn = (int)blockIdx.x / g.Rs;
-  const i64 SV = g.S / V, stride = (i64)g.Rs * BN_BLOCK;
-  const double x0 = (double)Tx::get(x[(i64)c * g.S]);       // the channel's first value: the origin of both sums
-  double s1 = 0.0, s2 = 0.0;
-  for (int n = rn; n < g.N; n += g.Rn) {
-    const typename Tx::T *xs = x + ((i64)n * g.C + c) * g.S;
-    for (i64 i = (i64)rs * BN_BLOCK + threadIdx.x; i < SV; i += stride) {
-      float a[V];
-      st_load<Tx, V>(xs + i * V, a);
-#pragma unroll
-      for (int j = 0; j < V; j++) {
-        const double d = (double)a[j] - x0;
-        s1 += d;
-        s2 += d * d;
-      }
-    }
-  }
-  bn_store_row(s1, s2, red, ws, g.Rs * g.Rn);
-}
-
+// bn_kernels.h's bn_train_apply term for term, with x (Tx, 16-bit) and y (Ty) on storage types and __restrict__ on both: x is
+// saved for the backward, so there is no in-place form.  A sibling, not one template with the fp32 kernel: that one's text (no
+// __restrict__ on x and y, the loop in bn_apply_share) costs these instantiations 1 to 3 instructions, and on the smallest
+// BatchNorm site of the model that form measured 2.2 % over the parent where 2 % is allowed (DESIGN.md;
+// profiles/r24a_bn_train_apply_timing.txt).  The statistics in front of it and both backward passes are bn_kernels.h's own kernels.
 template <typename Tx, typename Ty, int V>
 __global__ void __launch_bounds__(BN_BLOCK)
 bn_train_apply_mixed(const typename Tx::T *__restrict__ x, const float *__restrict__ rem, const float *__restrict__ weight,
@@ -91,86 +59,6 @@ bn_train_apply_mixed(const typename Tx::T *__restrict__ x, const float *__restri
         o[j] = relu ? relu_keep_nan(z) : z;
       }
       st_store<Ty, V>(y + base + i * V, o);
-    }
-  }
-}
-
-// ---- BatchNorm backward ------------------------------------------------------------------------------------------------------
-
-template <typename Tx, typename Ty, int V>
-__global__ void __launch_bounds__(BN_BLOCK)
-bn_bwd_partials_mixed(const typename Tx::T *__restrict__ x, const float *__restrict__ rem, const typename Ty::T *__restrict__ gy,
-                      const float *__restrict__ weight, const float *__restrict__ bias, const float *__restrict__ save_mean,
-                      const float *__restrict__ save_invstd, double *__restrict__ ws, BnGeom g, int relu)
-{
-  __shared__ double red[2 * BN_BLOCK];
-  const int c = (int)blockIdx.y, rs = (int)blockIdx.x % g.Rs, rn = (int)blockIdx.x / g.Rs;
-  const i64 SV = g.S / V, stride = (i64)g.Rs * BN_BLOCK;
-  const bool has_rem = rem != nullptr;
-  const float mean = save_mean[c];
-  float scale, shift;
-  bn_scale_shift(weight ? weight[c] : 1.f, bias ? bias[c] : 0.f, mean, save_invstd[c], scale, shift);
-  double s1 = 0.0, s2 = 0.0;
-  for (int n = rn; n < g.N; n += g.Rn) {
-    const i64 base = ((i64)n * g.C + c) * g.S;
-    for (i64 i = (i64)rs * BN_BLOCK + threadIdx.x; i < SV; i += stride) {
-      float a[V], r[V], d[V];
-      st_load<Tx, V>(x + base + i * V, a);
-      st_load<Ty, V>(gy + base + i * V, d);
-      if (relu && has_rem) st_load<st_f32, V>(rem + base + i * V, r);
-#pragma unroll
-      for (int j = 0; j < V; j++) {
-        float gj = d[j];
-        if (relu) gj = bn_z(a[j], scale, shift, has_rem ? r[j] : 0.f, has_rem) <= 0.f ? 0.f : gj;
-        s1 += (double)gj;
-        s2 += (double)gj * ((double)a[j] - (double)mean);
-      }
-    }
-  }
-  bn_store_row(s1, s2, red, ws, g.Rs * g.Rn);
-}
-
-// gx / grem / gw / gb: nullptr = not wanted.  With neither gx nor grem the launch is one block per channel (the parameter
-// gradients only) and `g` still names the rows the partial sums wrote.
-template <typename Tx, typename Ty, int V>
-__global__ void __launch_bounds__(BN_BLOCK)
-bn_bwd_apply_mixed(const typename Tx::T *__restrict__ x, const float *__restrict__ rem, const typename Ty::T *__restrict__ gy,
-                   const float *__restrict__ weight, const float *__restrict__ bias, const float *__restrict__ save_mean,
-                   const float *__restrict__ save_invstd, const double *__restrict__ ws, typename Tx::T *__restrict__ gx,
-                   float *__restrict__ grem, float *__restrict__ gw, float *__restrict__ gb, BnGeom g, int relu)
-{
-  BN_FP_STRICT
-  __shared__ double rows[2 * BN_MAX_ROWS];
-  const int c = (int)blockIdx.y;
-  double sg, sgx;
-  bn_sum_rows(ws, c, g.Rs * g.Rn, rows, sg, sgx);
-  const double M = (double)g.N * (double)g.S;
-  const float mean = save_mean[c], invstd = save_invstd[c];
-  const float k1 = (float)(sg / M), q = (float)((double)invstd * (double)invstd * sgx / M);
-  float scale, shift;
-  bn_scale_shift(weight ? weight[c] : 1.f, bias ? bias[c] : 0.f, mean, invstd, scale, shift);
-  if (blockIdx.x == 0 && threadIdx.x == 0) {        // once per channel
-    if (gw) gw[c] = (float)((double)invstd * sgx);
-    if (gb) gb[c] = (float)sg;
-  }
-  if (!gx && !grem) return;
-  const int rs = (int)blockIdx.x % g.Rs, rn = (int)blockIdx.x / g.Rs;
-  const i64 SV = g.S / V, stride = (i64)g.Rs * BN_BLOCK;
-  const bool has_rem = rem != nullptr;
-  for (int n = rn; n < g.N; n += g.Rn) {
-    const i64 base = ((i64)n * g.C + c) * g.S;
-    for (i64 i = (i64)rs * BN_BLOCK + threadIdx.x; i < SV; i += stride) {
-      float a[V], r[V], d[V], o[V];
-      st_load<Tx, V>(x + base + i * V, a);
-      st_load<Ty, V>(gy + base + i * V, d);
-      if (relu && has_rem) st_load<st_f32, V>(rem + base + i * V, r);
-#pragma unroll
-      for (int j = 0; j < V; j++) {
-        if (relu) d[j] = bn_z(a[j], scale, shift, has_rem ? r[j] : 0.f, has_rem) <= 0.f ? 0.f : d[j];
-        o[j] = scale * (d[j] - k1 - (a[j] - mean) * q);
-      }
-      if (gx) st_store<Tx, V>(gx + base + i * V, o);
-      if (grem) st_store<st_f32, V>(grem + base + i * V, d);
     }
   }
 }

@@ -1,4 +1,4 @@
-"""Mixed precision: the tails' conv32x1 on a 16-bit input (include/ganet_hip_conv16.h, ganet_amd/csrc/disp_conv16_kernels.h).
+"""Mixed precision: the tails' conv32x1 on a 16-bit input (include/ganet_hip_conv16.h, ganet_amd/csrc/disp_conv_kernels.h on a 16-bit storage type).
 
 Under torch.autocast the volume in front of conv32x1 is fp16 / bf16 and the tails behind it are fp32.  DispConv16Function reads
 the 16-bit x and the fp32 weight PARAMETER (not autocast's rounded copy) and returns an fp32 y; its data gradient is 16-bit,
@@ -64,7 +64,7 @@ def disp_conv16_grad_weight(x, grad_y, weight, native=True):
 
 class DispConv16Function(Function):
     """y fp32 [N,1,D,H,W] = conv3d(x fp16 | bf16 [N,C,D,H,W], weight fp32 [1,C,3,3,3], stride 1, padding 1) on the streaming
-    kernels of disp_conv16_kernels.h.  Saved: x and weight, nothing else; neither is written.  Only the gradients autograd asks
+    kernels of disp_conv_kernels.h.  Saved: x and weight, nothing else; neither is written.  Only the gradients autograd asks
     for are computed: grad_x in x's dtype, grad_weight fp32.  No state, no host synchronisation, any stream, capturable.
     `directions`, as DispConvFunction's: which of "forward", "data", "weight" run here; the others go to ATen's 16-bit
     convolution on the rounded weight (what torch.autocast does with the stock module), its result up-cast."""

@@ -1,4 +1,4 @@
-"""Mixed-precision TRAINING: autograd Functions over the 16-bit-storage kernels (ganet_amd/csrc/mixed_train_kernels.h and the
+"""Mixed-precision TRAINING: autograd Functions over the 16-bit-storage kernels (ganet_amd/csrc/bn_kernels.h, mixed_train_kernels.h and the
 forward entries of ganet_amd.functions.mixed), for a training step under torch.autocast: MIOpen's convolutions read and write
 fp16 / bf16, SGA, LGA and the tails stay fp32 with the backward they have, and no ATen cast pass stands between the two.
 

@@ -410,8 +410,8 @@ int ganet_l1_normalize_forward_mixed(const void *x, float *y0, float *y1, float 
                                      int N, int G, int C, int K, int H, int W, int x_type, void *stream);
 
 /* ABI v14 (additions).  Training under autocast: batch statistics on 16-bit storage and the backwards the inference entries
- * above left out (ganet_amd/csrc/mixed_train_kernels.h).  fp32 / fp64 arithmetic on the exactly up-cast operands, one rounding
- * on each 16-bit store.
+ * above left out (ganet_amd/csrc/bn_kernels.h on 16-bit storage types, mixed_train_kernels.h for the cost volume's adjoint).
+ * fp32 / fp64 arithmetic on the exactly up-cast operands, one rounding on each 16-bit store.
  *   bn train     ganet_bn_train_forward / _backward with a 16-bit x: their arithmetic term for term, their two launches each way
  *                over the same rows (ganet_bn_workspace is reused), no atomics, two runs bit-identical.  Three combinations:
  *                    x 16-bit, rem NULL, y and grad_y x's format   (every BasicConv)

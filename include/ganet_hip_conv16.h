@@ -2,7 +2,7 @@
  * ganet_hip_conv16.h -- C ABI of libganet_hip.so, additions to ABI v14 (GANET_ABI_VERSION stays 14; every entry of
  * ganet_hip.h is unchanged): the tails' conv32x1 = nn.Conv3d(C, 1, (3,3,3), (1,1,1), (1,1,1), bias=False)
  * (models/GANet_deep.py:212, 232) on a 16-bit x, so that torch.autocast keeps the streaming kernels of ganet_disp_conv_*
- * instead of the library's 16-bit one-column GEMM (ganet_amd/csrc/disp_conv16_kernels.h).
+ * instead of the library's 16-bit one-column GEMM (ganet_amd/csrc/disp_conv_kernels.h, instantiated on a 16-bit storage type).
  *
  * The conventions are ganet_hip.h's: device pointers to contiguous buffers, `stream` a hipStream_t passed as void *, 0 or a
  * negative GANET_E_* with a message in ganet_last_error().  fp16 and bf16 values are uint16_t patterns; x_type / gx_type is

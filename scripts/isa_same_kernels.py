@@ -1,6 +1,8 @@
 """Which kernels of two `hipcc -S --cuda-device-only` listings have the same instruction text (labels renumbered, comments dropped)?
-python scripts/isa_same_kernels.py old.s new.s  -- used to show that a new variant of a textually included kernel (lga_apply_pp.inc,
-lga_filter_grad_pp.inc) left every existing instantiation as it was."""
+python scripts/isa_same_kernels.py old.s new.s [renames.txt]  -- used to show that a new variant of a textually included kernel
+(lga_apply_pp.inc, lga_filter_grad_pp.inc) left every existing instantiation as it was.  Kernels are matched by mangled name;
+renames.txt holds `old-symbol new-symbol` pairs, one per line, for kernels to compare across a change of name or of template
+arguments (profiles/r24a_renames.txt).  A kernel of old.s that is neither in new.s nor mapped is reported as `missing`."""
 import re,sys
 def kernels(path):
     t=open(path).read().split('\n')
@@ -19,12 +21,15 @@ def kernels(path):
         i+=1
     return out
 a=kernels(sys.argv[1]); b=kernels(sys.argv[2])
-same=diff=0
+renames=dict(l.split() for l in open(sys.argv[3]) if l.strip() and not l.startswith('#')) if len(sys.argv)>3 else {}
+same=diff=renamed=0
 for k in a:
-    if k not in b: print('missing', k[:60]); continue
-    if a[k]==b[k]: same+=1
+    n=k if k in b else renames.get(k)
+    if n not in b: print('missing', k[:60]); continue
+    renamed+=n!=k
+    if a[k]==b[n]: same+=1
     else:
         diff+=1
-        d=[(x,y) for x,y in zip(a[k],b[k]) if x!=y][:2]
-        print('DIFF', k[:70], len(a[k]), len(b[k]), d)
-print('same',same,'diff',diff,'new',len(set(b)-set(a)))
+        d=[(x,y) for x,y in zip(a[k],b[n]) if x!=y][:2]
+        print('DIFF', k[:70], len(a[k]), len(b[n]), d)
+print('same',same,'diff',diff,'renamed',renamed,'new',len(set(b)-set(a)-{renames.get(k) for k in a}))

@@ -207,6 +207,9 @@ def by_name(name, kind="general"):
 ENTRIES = (("ganet_disp_conv_forward", 3), ("ganet_disp_conv_backward_data", 3), ("ganet_disp_conv_backward_weight", 4))
 
 
+BEYOND_WORKSPACE = (1, 64, 1024, 2048, 2048)         # inside the launch grid; rows * 27 * C = 2^21 * 1728 > 2^31 - 1
+
+
 def check_bad_arguments(api, dev):
     """the neighbouring entries' checks, plus C <= 64; a refused call launches nothing"""
     from ganet_amd._native import E_INVALID, E_UNSUPPORTED, GanetError
@@ -219,6 +222,8 @@ def check_bad_arguments(api, dev):
             (api.query if name.endswith("workspace") else api.call)(name, *args)
         except GanetError as e:
             assert text in str(e) and e.code == code, (name, args, str(e))
+            # the library's own message names the entry that was called (the launchers behind the fp32 and the _16 entries are shared)
+            assert str(e).startswith(f"{name} failed ({code}): {name}: "), (name, str(e))
         else:
             raise AssertionError((name, args))
 
@@ -235,6 +240,11 @@ def check_bad_arguments(api, dev):
             refused("null pointer", E_INVALID, name, *ptrs, *good, dev.stream)
         refused("at most 64", E_UNSUPPORTED, name, *p[:n], 1, 65, 1, 1, 1, dev.stream)
         refused("alias", E_INVALID, name, *([p[0]] * n), *good, dev.stream)
+        refused("beyond the launch grid", E_UNSUPPORTED, name, *p[:n], 65536, 1, 1, 1, 1, dev.stream)
+    # 16384 x 128 blocks = 2^21 workspace rows of 27 * 64 floats: past what ganet_disp_conv_workspace can answer, refused before any launch
+    refused("workspace is beyond ganet_disp_conv_workspace's answer", E_UNSUPPORTED, "ganet_disp_conv_backward_weight", *p[:4], *BEYOND_WORKSPACE, dev.stream)
+    refused("do not fit the answer", E_UNSUPPORTED, "ganet_disp_conv_workspace", *BEYOND_WORKSPACE)
+    refused("beyond the launch grid", E_UNSUPPORTED, "ganet_disp_conv_workspace", 65536, 1, 1, 1, 1)
     refused("at most 64", E_UNSUPPORTED, "ganet_disp_conv_workspace", 1, 65, 1, 1, 1)
     assert api.query("ganet_disp_conv_workspace", 1, 64, 1, 1, 1) == 27 * 64
     dev.sync()

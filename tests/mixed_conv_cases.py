@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE: the case table of conv32x1 on a 16-bit x (include/ganet_hip_conv16.h, ganet_amd/csrc/disp_conv16_kernels.h:
+"""TEST INFRASTRUCTURE: the case table of conv32x1 on a 16-bit x (include/ganet_hip_conv16.h, ganet_amd/csrc/disp_conv_kernels.h on a 16-bit storage type:
 ganet_disp_conv_forward_16 / _backward_data_16 / _backward_weight_16), run on the emulator behind guard pages by
 tests/test_sim_mixed_conv.py and on the device by tests/test_gpu_mixed_conv.py through one `dev` (parity_cases.NumpyDev /
 test_gpu_parity.TorchDev), in both 16-bit formats.
@@ -299,6 +299,8 @@ def check_bad_arguments(api, dev):
             api.call(name, *args)
         except GanetError as e:
             assert text in str(e) and e.code == code, (name, args, str(e))
+            # the library's own message names the entry that was called (the launchers behind the fp32 and the _16 entries are shared)
+            assert str(e).startswith(f"{name} failed ({code}): {name}: "), (name, str(e))
         else:
             raise AssertionError((name, args))
 
@@ -314,6 +316,9 @@ def check_bad_arguments(api, dev):
         refused("alias", E_INVALID, name, *([p[0]] * n), *good, mc.BF16, dev.stream)
         for code in (mc.F32, 3, -1):
             refused("type code", E_INVALID, name, *p[:n], *good, code, dev.stream)
+        refused("beyond the launch grid", E_UNSUPPORTED, name, *p[:n], 65536, 1, 1, 1, 1, mc.F16, dev.stream)
+    refused("workspace is beyond ganet_disp_conv_workspace's answer", E_UNSUPPORTED, "ganet_disp_conv_backward_weight_16", *p[:4],
+            *dc.BEYOND_WORKSPACE, mc.BF16, dev.stream)
     dev.sync()
     for b in bufs:
         assert np.isnan(np.asarray(dev.host(b))).all()

@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE: the case table of the mixed-precision TRAINING kernels (ganet_amd/csrc/mixed_train_kernels.h and
+"""TEST INFRASTRUCTURE: the case table of the mixed-precision TRAINING kernels (ganet_amd/csrc/bn_kernels.h, mixed_train_kernels.h and
 misc_kernels.h's l1norm_bwd<KT, Tx>: ganet_bn_train_forward_mixed / _backward_mixed, ganet_cost_volume_backward_16,
 ganet_l1_normalize_backward_mixed), run on the emulator by tests/test_sim_mixed_train.py and on the device by
 tests/test_gpu_mixed_train.py through one `dev` (parity_cases.NumpyDev / test_gpu_parity.TorchDev), as tests/mixed_cases.py is.

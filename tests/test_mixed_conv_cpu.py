@@ -32,11 +32,27 @@ needs_models = pytest.mark.skipif(not refmodel.available(), reason="no reference
 
 def test_case_table_reaches_what_it_claims():
     mcc.check_table()
-    hdr = open(os.path.join(ROOT, "ganet_amd", "csrc", "disp_conv16_kernels.h")).read()
-    assert '#include "disp_conv_kernels.h"' in hdr and "constexpr int DCV_" not in hdr, "the geometry is disp_conv_kernels.h's own"
-    for shared in ("dcv_lane(g)", "dcv_fma9(", "dcv_plane<VEC>(", "dcv_store4<VEC>(", "seg_allsum<64>(acc[j][t])", "(r0.x + r1.x) + (r2.x + r3.x)"):
+    # geometry and arithmetic are not merely shared with the fp32 kernels: they are the same text, with the storage type of the
+    # big volume as a template parameter, so there is no second copy that could drift
+    csrc = os.path.join(ROOT, "ganet_amd", "csrc")
+    assert not os.path.exists(os.path.join(csrc, "disp_conv16_kernels.h"))
+    hdr = open(os.path.join(csrc, "disp_conv_kernels.h")).read()
+    for kernel in ("disp_conv_fwd", "disp_conv_bwd_data", "disp_conv_bwd_weight_partials"):
+        assert len(re.findall(r"^%s\(" % kernel, hdr, re.M)) == 1, kernel
+        assert len(re.findall(r"template <typename ST, bool VEC>\nstatic __global__ void __launch_bounds__\(64 \* DCV_WAVES\)\n%s\(" % kernel, hdr)) == 1, kernel
+    assert len(re.findall(r"__global__", hdr)) == 4 and "disp_conv16" not in hdr        # (the fourth: disp_conv_bwd_weight_sum)
+    for const in ("DCV_WAVES", "DCV_PX", "DCV_DEPTH", "DCV_CB"):
+        assert hdr.count("constexpr int %s = " % const) == 1, const
+    assert hdr.count("fmaf(") == 3, "one FMA chain per direction, whatever the storage type"
+    for shared in ("dcv_lane(g)", "dcv_fma9(", "dcv_plane<VEC>(", "dcv_store4<st_f32, VEC>(y + ", "dcv_store4<ST, VEC>(gx + ", "dcv_own4<ST, VEC>(x + ",
+                   "seg_allsum<64>(acc[j][t])", "(r0.x + r1.x) + (r2.x + r3.x)"):
         assert shared in hdr, shared
-    assert "atomic" not in hdr
+    assert hdr.count("dcv_lane(g)") == 3 and hdr.count("seg_allsum<64>(acc[j][t])") == 1 and hdr.count("(r0.x + r1.x) + (r2.x + r3.x)") == 1
+    assert "atomic" not in re.sub(r"//[^\n]*", "", hdr)                 # (the header's comment says "no atomics"; the code has none)
+    # the host side: each direction is launched from one place, by the fp32 entry and by the _16 entry
+    capi = open(os.path.join(csrc, "ganet_capi.hip")).read()
+    for kernel in ("disp_conv_fwd<", "disp_conv_bwd_data<", "disp_conv_bwd_weight_partials<", "disp_conv_bwd_weight_sum,"):
+        assert capi.count("GA_LAUNCH((" + kernel) + capi.count("GA_LAUNCH(" + kernel) == 1, kernel
 
 
 @pytest.mark.parametrize("fmt", mcc.FMTS, ids=fmt_id)

@@ -1,4 +1,4 @@
-"""conv32x1 on a 16-bit x (ganet_amd/csrc/disp_conv16_kernels.h: ganet_disp_conv_forward_16 / _backward_data_16 /
+"""conv32x1 on a 16-bit x (ganet_amd/csrc/disp_conv_kernels.h on a 16-bit storage type: ganet_disp_conv_forward_16 / _backward_data_16 /
 _backward_weight_16) on the CPU emulator build: the case table of tests/mixed_conv_cases.py (tests/test_gpu_mixed_conv.py runs the
 same table on the device), in both formats and both guard modes -- each buffer ENDS at an inaccessible page, resp. BEGINS right
 behind one -- with the workspace and every output pre-filled with NaN patterns.  Equality of bits throughout: against the fp32

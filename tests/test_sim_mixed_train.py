@@ -1,4 +1,4 @@
-"""The mixed-precision training kernels (ganet_amd/csrc/mixed_train_kernels.h, l1norm_bwd<KT, Tx>) on the CPU emulator build: the
+"""The mixed-precision training kernels (ganet_amd/csrc/bn_kernels.h, mixed_train_kernels.h, l1norm_bwd<KT, Tx>) on the CPU emulator build: the
 case table of tests/mixed_train_cases.py (tests/test_gpu_mixed_train.py runs the same table on the device), every buffer at a
 guard page -- ENDING at one, resp. BEGINNING right behind one -- and every output pre-filled with a NaN pattern.  What is checked
 and why is in the table's docstring; the first tests hold the table to what it claims."""
